@@ -22,10 +22,18 @@ Under torchrun / mpiexec / srun (RANK+WORLD_SIZE set) it runs as one rank.
 Data: synthetic N(0,1) windows generated on device (the reference's synthetic shard distribution,
 Module_1/shard_prep.py:35-37), dummy zero labels (Module_3/shard_dataset.py:70), random-init weights.
 
-Extra fields: ``torch_eager_*`` (same step in eager PyTorch bf16-autocast, the reference's G1 code path,
-measured in the same process) and ``conv1d_*`` (Module-2 kernel vs torch.nn.Conv1d, B=256, K=7; the
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the JSON line.
+
+``--full`` adds the extra fields: ``torch_eager_*`` (same step in eager PyTorch bf16-autocast, the reference's G1
+code path, measured in the same process) and ``conv1d_*`` (Module-2 kernel vs torch.nn.Conv1d, B=256, K=7; the
 headline ``conv1d_speedup_vs_torch`` uses the reference's single-call ``time_once`` metric,
 Module_2/benchmark_part_2.py:61-67,108).
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step left on rank 0 - ``weights.npy``
+(the flat fp32 weights after the final FedAvg), ``momentum.npy`` (the client's SGD momentum, when the trainer
+keeps a flat one) and ``avg_loss.npy`` (float64 mean loss of the last round) - so two builds run with the same
+arguments (same seeds, same synthetic shard) can be compared output for output.  At most 64 MB in all: a larger
+array is stored as a fixed seeded sample of its elements.
 """
 from __future__ import annotations
 
@@ -61,7 +69,14 @@ def parse(argv=None):
                          "(exact FedAvg, bitwise equal to none)")
     ap.add_argument("--device", choices=["gpu", "cpu"], default="gpu",
                     help="cpu: plumbing rehearsal of the launch/sync/JSON contract (gloo, eager torch)")
-    ap.add_argument("--no-extras", action="store_true", help="skip torch-eager and conv1d side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements (torch-eager baseline of the same step, "
+                         "conv1d vs torch.nn.Conv1d); a plain run only sets up, warms up, times the steps and prints")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="skip the side measurements even with --full (a plain run never takes them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step left (flat weights, momentum, average "
+                         "loss of the last round) to DIR/<name>.npy")
     ap.add_argument("--no-numa-bind", action="store_true",
                     help="keep the inherited CPU affinity (default: each rank pins itself to its GPU's NUMA node)")
     return ap.parse_args(argv)
@@ -180,6 +195,28 @@ def weights_digest(flat):
     """float64 sum and abs-sum of the flat weights plus their first and last 8 values (18 numbers)."""
     f = flat.detach().double()
     return [float(f.sum()), float(f.abs().sum())] + f[:8].tolist() + f[-8:].tolist()
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write ``arrays`` (name -> tensor or None) as ``directory/<name>.npy`` in float32 (float64 stays float64),
+    ``budget`` bytes at most in all: an array larger than its equal share of the budget is stored as a fixed
+    sample of its flattened elements (indices drawn once from a seeded generator, ascending)."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = budget // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        v = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).contiguous().numpy()
+        keep = share // v.itemsize
+        if v.size > keep:
+            sel = np.sort(np.random.default_rng(20240229).choice(v.size, size=keep, replace=False))
+            v = v.reshape(-1)[sel]
+        np.save(os.path.join(directory, name + ".npy"), v)
 
 
 def torch_eager_rate(x, y, B, steps, device):
@@ -429,15 +466,20 @@ def main(argv=None):
     value = total / elapsed
     loss = trainer.avg_loss() if hasattr(trainer, "avg_loss") else float("nan")
 
+    if a.dump_outputs and ctx.rank == 0:
+        dump_outputs(a.dump_outputs, {"weights": flat, "momentum": getattr(trainer, "mom", None),
+                                      "avg_loss": torch.tensor([loss], dtype=torch.float64)})
+
     extras = {}
-    if ctx.rank == 0 and not a.no_extras and resnet:
+    side = a.full and not a.no_extras  # side measurements: only on request, after the timed steps
+    if ctx.rank == 0 and side and resnet:
         try:
             from crossscale_ecg.bench.resnet import train_throughput
             extras["torch_eager_samples_per_s_per_gpu"] = round(train_throughput("torch", B=B, L=a.win_len), 1)
             extras["speedup_vs_torch_eager_per_gpu"] = round(value / a.gpus / extras["torch_eager_samples_per_s_per_gpu"], 2)
         except Exception as e:  # pragma: no cover
             extras["torch_eager_error"] = repr(e)[:200]
-    elif ctx.rank == 0 and not a.no_extras:
+    elif ctx.rank == 0 and side:
         try:
             extras["torch_eager_samples_per_s_per_gpu"] = round(torch_eager_rate(x, y, B, 100, dev), 1)
             extras["speedup_vs_torch_eager_per_gpu"] = round(value / a.gpus / extras["torch_eager_samples_per_s_per_gpu"], 2)

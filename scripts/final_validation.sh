@@ -17,7 +17,7 @@ step() {  # step <name> <timeout_s> <cmd...>
 python csrc/build.py > "$OUT/build.log" 2>&1 || { cat "$OUT/build.log"; exit 2; }
 step pytest_gpu 900 python -u -m pytest tests -m gpu -v -p no:cacheprovider --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-for i in 1 2 3; do step bench20_$i 300 python bench.py --steps 20 --warmup 5; done
+for i in 1 2 3; do step bench20_$i 300 python bench.py --steps 20 --warmup 5 --full; done
 step bench500 300 python bench.py --steps 500 --warmup 100 --no-extras
 for i in 1 2; do step resnet_$i 300 python bench.py --model resnet1d34 --steps 20 --warmup 5 --no-extras; done
 export TMPDIR=/tmp

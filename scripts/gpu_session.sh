@@ -35,7 +35,7 @@ for s in "$@"; do
     smoke)
       step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     bench)
-      for i in 1 2 3; do step bench20_$i 300 python bench.py --steps 20 --warmup 5; done
+      for i in 1 2 3; do step bench20_$i 300 python bench.py --steps 20 --warmup 5 --full; done
       step bench500 300 python bench.py --steps 500 --warmup 100 --no-extras ;;
     bench20)
       for i in 1 2 3; do step bench20_$i 300 python bench.py --steps 20 --warmup 5 --no-extras; done ;;

@@ -44,3 +44,19 @@ def test_bench_resnet_contract():
     rec = _bench("--model", "resnet1d34", "--batch-size", "64", "--steps", "3", "--warmup", "2", "--no-extras")
     _check(rec, 3, 2, 64)
     assert rec["config"]["model"].startswith("resnet1d34")
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run takes no side measurement; --dump-outputs writes the last timed step's weights, momentum and
+    average loss as float32 / float64 .npy files."""
+    import numpy as np
+    rec = _bench("--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path / "out"))
+    _check(rec, 20, 5, 256)
+    assert not [k for k in rec if k.startswith(("torch_eager", "conv1d_", "speedup_vs"))]
+    w, m = np.load(tmp_path / "out" / "weights.npy"), np.load(tmp_path / "out" / "momentum.npy")
+    loss = np.load(tmp_path / "out" / "avg_loss.npy")
+    assert w.dtype == np.float32 and m.dtype == np.float32 and loss.dtype == np.float64
+    assert w.ndim == 1 and w.shape == m.shape and w.size >= 1458 and loss.shape == (1,)  # flat buffer incl. padding
+    assert np.isfinite(w).all() and np.isfinite(m).all() and np.abs(m).max() > 0
+    assert float(loss[0]) == pytest.approx(rec["final_avg_loss"], abs=1e-6)
+    assert float(w.astype(np.float64).sum()) == pytest.approx(rec["fedavg_weights_checksum"], rel=1e-6, abs=1e-6)

@@ -68,3 +68,38 @@ def test_bench_world2_fedavg_weights_identical_and_tail_equals_none():
         assert "overlap=" + ov in rec["config"]["sync"]
     assert recs["none"]["fedavg_weights_checksum"] == recs["tail"]["fedavg_weights_checksum"]
     assert recs["none"]["final_avg_loss"] == recs["tail"]["final_avg_loss"]
+
+
+def test_bench_dump_outputs_same_arguments_same_arrays(tmp_path):
+    """--dump-outputs: the same arguments give the same inputs, so two runs write identical arrays; the plain run's
+    JSON line carries no side measurement."""
+    import numpy as np
+    out = []
+    for name in ("a", "b"):
+        rec = _bench("--steps", "3", "--warmup", "1", "--local-steps", "2", "--dump-outputs", str(tmp_path / name))
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert not [k for k in rec if k.startswith(("torch_eager", "conv1d_", "speedup_vs"))]
+        out.append({f: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    assert set(out[0]) == {"weights.npy", "avg_loss.npy"}  # the eager CPU trainer keeps its momentum in the optimizer
+    w = out[0]["weights.npy"]  # the flat buffer: 1,458 parameters plus alignment padding
+    assert w.dtype == np.float32 and w.ndim == 1 and w.size >= 1458 and np.isfinite(w).all()
+    assert out[0]["avg_loss.npy"].dtype == np.float64
+    for f in out[0]:
+        assert np.array_equal(out[0][f], out[1][f]), f
+
+
+def test_dump_outputs_samples_large_arrays_within_budget(tmp_path):
+    """An array larger than its share of the byte budget is stored as a fixed sample: same indices every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(10000, dtype=torch.float32)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), {"big": big, "small": torch.ones(3, dtype=torch.float64),
+                                                  "none": None}, budget=8000)
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.shape == (1000,) and a.dtype == np.float32 and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a.nbytes + 24 <= 8000
+    assert np.load(tmp_path / "a" / "small.npy").dtype == np.float64
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "small.npy"]
