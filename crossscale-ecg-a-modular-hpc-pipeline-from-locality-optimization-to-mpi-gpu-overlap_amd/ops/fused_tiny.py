@@ -1,6 +1,8 @@
 """Fused TinyECG training / inference on gfx950 (Python side of csrc/kernels/tiny_ecg_step.hip).
 
-Each workgroup computes one sample's forward+backward out of LDS.  ``FusedTinyTrainer`` runs a whole FedAvg
+Each workgroup computes one sample's forward+backward out of LDS.  The bf16 kernels keep no copy of the window
+there: every wave builds its conv1 operand in registers from bounded loads of the window row in global memory
+(the fp32 kernel stages the window in LDS for its VALU conv1).  ``FusedTinyTrainer`` runs a whole FedAvg
 local round as two launches per step (gradient slab, then slab reduction + SGD), captured into one native hipGraph
 and replayed with a single ``hipGraphLaunch`` per round.  (A one-launch step with an in-kernel reduction tree and a
 persistent one-launch round were measured slower on MI355X and removed in round 5: profiles/r4/tiny_phase_diag.txt.)
@@ -53,7 +55,7 @@ def _wprep_ptr(precision: str, prefrag: Optional[bool], device, wprep: Optional[
 
 def gather_default() -> bool:
     """PF round graphs gather every step's windows and labels into a contiguous ping-pong buffer inside the
-    previous step's reduce launch (on by default; the ``gather`` attribute of a trainer), so the step kernel stages row b without the
+    previous step's reduce launch (on by default; the ``gather`` attribute of a trainer), so the step kernel reads row b without the
     dependent idx -> window load (csrc/kernels/tiny_ecg_step.hip GatherArgs).  Measured: step kernel 7.76 -> 7.52
     us and step period 12.35 -> 12.08 us under the kernel tracer (medians of 687 steps), bench K=500 11.17 -> 11.06
     us/step (profiles/r3/tiny_gather_ab.txt)."""

@@ -1,7 +1,9 @@
 // Fused TinyECG training step for gfx950 (MI355X, CDNA4).
 //
 // One workgroup owns one ECG window and runs the WHOLE per-sample training computation out of LDS:
-//   gather x[idx[b]]  ->  conv1(1->16,k7,p3)+bias+ReLU (VALU)  ->  conv2(16->16,k5,p2)+bias+ReLU
+//   gather x[idx[b]]  ->  conv1(1->16,k7,p3)+bias+ReLU (bf16: MFMA, each wave builds its im2col operand in
+//   registers straight from the global window row, no LDS copy of the window; fp32: VALU over the window staged in
+//   LDS)  ->  conv2(16->16,k5,p2)+bias+ReLU
 //   (MFMA bf16 16x16x32, implicit GEMM M=t, N=c_out, K=(tap,c_in)=80->96)  ->  mean-pool  ->
 //   Linear(16->C)  ->  softmax-CE  ->  head grads  ->  dconv2 wgrad (MFMA, dh2 kept in the MFMA
 //   accumulator layout and used directly as the A operand; h1 read as the B operand with the gfx950
@@ -48,7 +50,8 @@ __host__ __device__ inline Layout make_layout(int nc) {
   return l;
 }
 
-// LDS carve (bytes), all offsets multiples of 16.
+// LDS carve (bytes), all offsets multiples of 16.  fp32: the window xs, then the activations; bf16 has no xs (conv1
+// reads the window from global memory) and starts with the conv1 im2col rows xcol, kept for the conv1 wgrad.
 struct Smem {
   int Lp;  // L rounded up to 32 (tile pairs)
   int xs_off, xcol_off, h1_off, dh2_off, ps_off, frag_off, red_off, bytes;
@@ -87,6 +90,12 @@ __device__ __forceinline__ void st_wt4(__amdgpu_buffer_rsrc_t r, int idx, f32x4 
 __device__ __forceinline__ float ld_wt(__amdgpu_buffer_rsrc_t r, int idx) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, idx * 4, 0, 16));
 }
+// Plain (cached) bounded load: a byte offset at or past the resource's size reads 0.  Callers keep every offset
+// non-negative and below 2^31 so no sum of offsets wraps.
+__device__ __forceinline__ float ld_bounded(__amdgpu_buffer_rsrc_t r, int byte_off) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
+}
+constexpr int kOobByte = 0x40000000;  // past every window row (L <= 1024 floats), far from wrapping with + 4j
 
 // fp32 path: v_mfma_f32_16x16x4_f32 (exact f32 products, K = 80 = 20 k-steps of 4, no padding)
 constexpr int F32_KSTEPS = C * K2 / 4;
@@ -162,8 +171,8 @@ __host__ __device__ inline Smem make_smem(int L, int waves, int nc = MAX_CLASSES
   Smem s;
   s.Lp = (L + 31) / 32 * 32;
   s.xs_off = 0;
-  // fp32 window xs[Lp + 16]; bf16 adds the conv1 im2col rows xcol[Lp + 1][8] (row Lp = zeros)
-  s.xcol_off = s.xs_off + ((s.Lp + 16) * 4 + 15) / 16 * 16;
+  // fp32: window xs[Lp + 16]; bf16: the conv1 im2col rows xcol[Lp + 1][8] (row Lp = zeros) and no xs
+  s.xcol_off = s.xs_off + (f32 ? ((s.Lp + 16) * 4 + 15) / 16 * 16 : 0);
   s.h1_off = s.xcol_off + (f32 ? 0 : (s.Lp + 1) * 16);
   const int act_bytes = (s.Lp + 8) * C * (f32 ? 4 : 2);  // [Lp+8][16] in the activation type
   s.dh2_off = s.h1_off + act_bytes;
@@ -230,8 +239,9 @@ struct TinySample {
   Layout lay;
   int L, Lp, NP, nc;
   int tid, lane, w, h, c;  // h: lane quarter, c: channel owned by this lane in C-layout phases
-  float* xs;               // [Lp + 16]: xs[i] = x[i - 3] (conv1 halo)
-  __bf16* xcol;            // bf16 path: [Lp + 1][8]: {x[t-3..t+3], t < L} (0 for t >= L), row Lp = zeros
+  float* xs;               // fp32 path: [Lp + 16]: xs[i] = x[i - 3] (conv1 halo)
+  __bf16* xcol;            // bf16 path: [Lp + 1][8]: {x[t-3..t+3], t < L} (0 for t >= L), row Lp = zeros;
+                           // written by conv1 (a copy of its register operand), read by the conv1 wgrad
   AT* h1s;                 // row (t+2): h1[t][ci]
   AT* ms;                  // row (t+4): m[t][co] = relu'(h2) in {0,1}
   float* ps;               // fp32 copy of the flat params
@@ -241,8 +251,19 @@ struct TinySample {
   float* fragD32;          // fp32 path: [20][64] dgrad B operand
   float* red;
   uint32_t mask1 = 0u;     // relu'(h1) bits of this lane's conv1 outputs (phase 1 -> phase 4)
-  // PF: this lane's conv operands in registers, loaded from the global image (phase 0 / end of phase 2)
+  // PF: this lane's conv operands in registers, loaded from the global image (phase 0 / end of phase 2).
+  // pf_aw (conv1's A operand) is register-resident in the LDS-built bf16 kernel too (load_aw).
   bf16x8 pf_aw, pf_wf[3], pf_wd[3];
+
+  // LDS-built bf16 kernel: conv1's A operand row {w1[c][0..6], b1[c]} straight from the flat parameters (the same
+  // bf16 values as the image's WP_AW1 row), so conv1 reads nothing that another thread staged.
+  __device__ __forceinline__ void load_aw(const float* __restrict__ params) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float v = j < K1 ? params[lay.w1 + c * K1 + j] : params[lay.b1 + c];
+      pf_aw[j] = ecg::to_bf16(h == 0 ? v : 0.f);
+    }
+  }
 
   __device__ __forceinline__ void pf_load_fwd(const unsigned char* __restrict__ wp) {
     const __bf16* wb = reinterpret_cast<const __bf16*>(wp);
@@ -286,8 +307,8 @@ struct TinySample {
   }
 
   // ---- phase 0: window, parameters, constant pads
-  // The window goes global -> registers (load_x) -> LDS (put_x): xs elements i = tid + k*NT, one coalesced load
-  // each.
+  // fp32: the window goes global -> registers (load_x) -> LDS (put_x): xs elements i = tid + k*NT, one coalesced
+  // load each.  bf16 stages no window: conv1_load below.
   static constexpr int XK = (32 * MAX_PAIRS_PER_WAVE * WAVES + 16 + NT - 1) / NT;
   struct XRegs {
     float v[XK];
@@ -313,6 +334,46 @@ struct TinySample {
     XRegs r;
     load_x(xrow, r);
     put_x(r);
+  }
+
+  // bf16: the conv1 B operand of tile pair (pi, pi + 1) of this wave, fetched by the lanes that use it.  Lane n of
+  // quarter 0 loads the 7 window floats x[t-3 .. t+3] of its time step t = 16*tile + n through ``xr``, a buffer
+  // resource over exactly the row's L floats: elements past the row's end read 0 (the conv padding) without a
+  // branch, and quarters 1..3 and steps t >= L (whose operand is all zero) load from an out-of-range offset.
+  // Offsets never go negative: the three steps t < 3, whose window starts before the row, load x[0 .. 6] and
+  // conv1_operand shifts their values into place (tile 0 only: every other wave skips that branch).
+  struct X1 {
+    float v[2][K1];
+  };
+  __device__ __forceinline__ int conv1_t(int pi, int u) const {  // (clamped: the pair's second tile may not exist)
+    return 16 * min(w + (pi + u) * WAVES, Lp / 16 - 1) + (lane & 15);
+  }
+  __device__ __forceinline__ void conv1_load(__amdgpu_buffer_rsrc_t xr, int pi, X1& r) const {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int t = conv1_t(pi, u);
+      const int base = (h == 0 && t < L) ? 4 * max(t - 3, 0) : kOobByte;
+#pragma unroll
+      for (int j = 0; j < K1; ++j) r.v[u][j] = ld_bounded(xr, base + 4 * j);
+    }
+  }
+  // The loaded values as the MFMA operand {bf16(x[t-3 .. t+3]), "t < L"} (all zero in quarters 1..3 and for t >= L).
+  __device__ __forceinline__ bf16x8 conv1_operand(const float (&ld)[K1], int t) const {
+    float v[K1];
+#pragma unroll
+    for (int j = 0; j < K1; ++j) v[j] = ld[j];
+    if (h == 0 && t < 3) {  // v[j] = x[j] so far; wanted x[t + j - 3], 0 before the row: shift up by 3 - t
+      const int s = 3 - t;
+#pragma unroll
+      for (int j = K1 - 1; j >= 0; --j) v[j] = (s & 1) ? (j >= 1 ? v[j - 1] : 0.f) : v[j];
+#pragma unroll
+      for (int j = K1 - 1; j >= 0; --j) v[j] = (s & 2) ? (j >= 2 ? v[j - 2] : 0.f) : v[j];
+    }
+    bf16x8 Bx;
+#pragma unroll
+    for (int j = 0; j < K1; ++j) Bx[j] = ecg::to_bf16(v[j]);
+    Bx[7] = ecg::to_bf16(h == 0 && t < L ? 1.f : 0.f);
+    return Bx;
   }
 
   // One flat parameter -> its fp32 LDS copy and, for conv2 weights w2[co][ci][k], the MFMA B fragments in
@@ -362,67 +423,49 @@ struct TinySample {
     }
   }
 
-  // ---- phase 1: conv1 + bias + ReLU into h1s (bf16: MFMA over the im2col rows; fp32: VALU)
-  __device__ __forceinline__ void conv1() {
-    if constexpr (!F32) {
-      // A = W1ext[co][kk]: quarter 0 holds kk 0..7 (taps, then the bias), quarters 1..3 the zero K padding
-      bf16x8 Aw;
-      if constexpr (PF) {
-        Aw = pf_aw;
-      } else {
+  // ---- phase 1: conv1 + bias + ReLU into h1s (bf16: MFMA, conv1_mfma; fp32: VALU, conv1)
+  // bf16.  A = W1ext[co][kk] (pf_aw): quarter 0 holds kk 0..7 (taps, then the bias), quarters 1..3 the zero K
+  // padding.  B = xcol[t][kk], K = 32: quarter 0 holds {bf16(x[t-3 .. t+3]), "t < L"} built in registers from its
+  // own loads (conv1_load / conv1_operand), quarters 1..3 hold zeros.  Quarter 0 also stores its operand as the
+  // im2col row t (one 16-byte LDS store) for phase 4's conv1 wgrad; nothing reads xcol before the phase-1 barrier.
+  __device__ __forceinline__ void conv1_pair(int pi, const X1& x) {
+    const bool has2 = w + (pi + 1) * WAVES < Lp / 16;
+    bf16x8 Bx[2];
+    int t[2];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float v = j < K1 ? ps[lay.w1 + c * K1 + j] : ps[lay.b1 + c];
-          Aw[j] = ecg::to_bf16(h == 0 ? v : 0.f);
-        }
-      }
-      // B = xcol[t][kk] (K = 32: quarter 0 holds kk 0..7, quarters 1..3 read the zero row Lp).  The four lane
-      // quarters build each im2col row together (quarter h writes columns 2h, 2h+1 of row t = 16*tile + n;
-      // column 7 = bias x "t < L"), quarter 0 reads the whole row back as its operand.  Tiles go two at a time
-      // with every LDS access of a kind issued for both before the next kind (one round trip per kind, not per
-      // tile); each wave only reads rows it wrote itself (same-wave LDS order, no barrier).
-      const __bf16* xb = xcol + (h == 0 ? (lane & 15) * 8 : Lp * 8);
-      const int tstride = h == 0 ? 16 * 8 : 0;
-      const int ntiles = Lp / 16;
-      const int j0 = 2 * h;
-#pragma unroll 1
-      for (int pi = 0; pi < 2 * MAX_PAIRS_PER_WAVE; pi += 2) {
-        if (w + pi * WAVES >= ntiles) break;  // wave-uniform
-        int tile[2];
-        float v0[2], v1[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          tile[u] = min(w + (pi + u) * WAVES, ntiles - 1);  // clamped: the second tile may not exist
-          const int t = 16 * tile[u] + (lane & 15);
-          v0[u] = xs[t + j0];
-          v1[u] = j0 + 1 < K1 ? xs[t + j0 + 1] : 1.f;
-        }
-        const bool has2 = w + (pi + 1) * WAVES < ntiles;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int t = 16 * tile[u] + (lane & 15);
-          const bool tv = t < L;
-          bf16x2 pr;
-          pr[0] = ecg::to_bf16(tv ? v0[u] : 0.f);
-          pr[1] = ecg::to_bf16(tv ? v1[u] : 0.f);
-          *reinterpret_cast<bf16x2*>(xcol + t * 8 + j0) = pr;  // (a clamped duplicate rewrites the same values)
-        }
-        bf16x8 Bx[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) Bx[u] = *reinterpret_cast<const bf16x8*>(xb + tile[u] * tstride);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          if (u == 1 && !has2) break;
-          const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Aw, Bx[u], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          // acc[i] = conv1(x)[t = 16*tile + (lane&15)][co = 4h + i] + bias (exactly 0 for t >= L)
-          bf16x4 o;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) o[i] = (AT)fmaxf(acc[i], 0.f);
-          *reinterpret_cast<bf16x4*>(h1s + (16 * tile[u] + (lane & 15) + 2) * C + 4 * h) = o;
-        }
-      }
-      return;
+    for (int u = 0; u < 2; ++u) {
+      t[u] = conv1_t(pi, u);
+      Bx[u] = conv1_operand(x.v[u], t[u]);
+      // (a clamped duplicate tile rewrites the same values)
+      if (h == 0) *reinterpret_cast<bf16x8*>(xcol + t[u] * 8) = Bx[u];
     }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if (u == 1 && !has2) break;
+      const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf_aw, Bx[u], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+      // acc[i] = conv1(x)[t][co = 4h + i] + bias (exactly 0 for t >= L)
+      bf16x4 o;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[i] = (AT)fmaxf(acc[i], 0.f);
+      *reinterpret_cast<bf16x4*>(h1s + (t[u] + 2) * C + 4 * h) = o;
+    }
+  }
+  // ``x0``: the wave's first pair, whose loads phase 0 issued.  Further pairs (8 waves or windows past 512 steps)
+  // load their own.
+  __device__ __forceinline__ void conv1_mfma(__amdgpu_buffer_rsrc_t xr, const X1& x0) {
+    const int ntiles = Lp / 16;
+    if (w < ntiles) conv1_pair(0, x0);  // wave-uniform
+#pragma unroll 1
+    for (int pi = 2; pi < 2 * MAX_PAIRS_PER_WAVE; pi += 2) {
+      if (w + pi * WAVES >= ntiles) break;  // wave-uniform
+      X1 x;
+      conv1_load(xr, pi, x);
+      conv1_pair(pi, x);
+    }
+  }
+
+  __device__ __forceinline__ void conv1() {
+    static_assert(F32, "bf16 kernels run conv1_mfma");
     mask1 = 0u;
     float w1r[K1];
 #pragma unroll
@@ -978,22 +1021,26 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
 #define ECG_STAMP(k) \
   if (stamps && tid == 0) stamps[(long)b * 16 + 7 * rep + (k)] = __builtin_amdgcn_s_memtime();
     ECG_STAMP(0)
-    // phase 0: stage params + x into LDS, zero pads.  (Measured: pre-gathering a round's windows into contiguous
-    // buffers inside the round graph, to drop the dependent idx -> row load, costs more than it saves:
+    // phase 0: stage params (fp32: + x) into LDS, zero pads.  (Measured: pre-gathering a round's windows into
+    // contiguous buffers inside the round graph, to drop the dependent idx -> row load, costs more than it saves:
     // 12.98 vs 12.52 us/step, profiles/r1_round_kernel/ab_pregather.log.)
     // The parameter loads are issued first, into registers, so their round trip overlaps the dependent
-    // idx -> window chain instead of following the window's LDS stores.
+    // idx -> window chain.  bf16: the window never goes to LDS - each wave issues the loads of its first conv1
+    // operand pair here (conv1_load) and phase 1 starts without a barrier: conv1 reads only its own registers, and
+    // the pads and head parameters written here are first read after the phase-1 barrier.  Stamp 1 then marks
+    // "inputs issued, pads written", not a barrier; the wait for the window is counted in phase 1.
     int ylab = 0;
+    const long row = idx ? (long)idx[b] : (long)b;
+    const float* xrow = X + row * ldx;
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t xr = make_rsrc(xrow, (long)L * 4);  // exactly the row (bf16)
+    [[maybe_unused]] typename TinySample<WAVES, F32, PF>::X1 x0;
     if constexpr (PF) {
       // conv operands: global image -> VGPRs; only the head's parameters go to LDS (plain fp32 copy)
       S.pf_load_fwd(wprep);
       const int i = S.lay.wh + tid;
       const float hv = i < S.lay.P ? params[i] : 0.f;
-      {
-        const long row = idx ? (long)idx[b] : (long)b;
-        if (TRAIN) ylab = Y[row];
-        S.stage_x(X + row * ldx);
-      }
+      if (TRAIN) ylab = Y[row];
+      S.conv1_load(xr, 0, x0);
       if (i < S.lay.P) S.ps[i] = hv;
       static_assert(MAX_CLASSES * C + MAX_CLASSES <= 8 * 64, "head parameters: one per thread");
     } else {
@@ -1004,10 +1051,12 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
         const int i = tid + j * S.NT;
         pv[j] = i < S.lay.P ? params[i] : 0.f;
       }
-      {
-        const long row = idx ? (long)idx[b] : (long)b;
-        if (TRAIN) ylab = Y[row];  // label prefetched with the window (used by the head)
-        S.stage_x(X + row * ldx);
+      if constexpr (!F32) S.load_aw(params);
+      if (TRAIN) ylab = Y[row];  // label prefetched with the window (used by the head)
+      if constexpr (F32) {
+        S.stage_x(xrow);
+      } else {
+        S.conv1_load(xr, 0, x0);
       }
 #pragma unroll
       for (int j = 0; j < PR; ++j) {
@@ -1017,9 +1066,14 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
       for (int i = tid + PR * S.NT; i < S.lay.P; i += S.NT) S.put_param(i, params[i]);
     }
     S.zero_pads();
-    __syncthreads();
-    ECG_STAMP(1)
-    S.conv1();
+    if constexpr (F32) {
+      __syncthreads();
+      ECG_STAMP(1)
+      S.conv1();
+    } else {
+      ECG_STAMP(1)
+      S.conv1_mfma(xr, x0);
+    }
     __syncthreads();
     ECG_STAMP(2)
     S.conv2();

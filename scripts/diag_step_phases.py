@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Diagnostic: where the fused TinyECG step spends its cycles (s_memtime stamps, wave 0 of each WG).
 
-Phases: 0 stage x/params | 1 conv1 | 2 conv2 fwd + mask | 3 head || mask-weighted wgrad | 4 dgrad2 + wgrad1 |
-5 row store.  Reports
+Phases: 0 issue the input loads (params, label, the wave's first conv1 window loads), head params + zero pads to
+LDS; ends without a barrier | 1 conv1 (starts with the wait for the window loads) | 2 conv2 fwd + mask |
+3 head || mask-weighted wgrad | 4 dgrad2 + wgrad1 | 5 row store.  Reports
   * hipEvent times of the gradient-only kernel and the two-launch round (LDS-built and prepared operands);
   * the per-step kernel's phases cold (first pass of a launch) and warm (MODE 2: the same workgroup computes
     its sample again right after, with warm instruction / scalar / data caches);
@@ -20,7 +21,7 @@ from crossscale_ecg.models.tiny_ecg import TinyECG  # noqa: E402
 from crossscale_ecg.ops import _lib  # noqa: E402
 from crossscale_ecg.ops.fused_tiny import tiny_step_grads, labels_int32, slab_stride, FusedTinyTrainer  # noqa: E402
 
-NAMES = ["stage", "conv1", "conv2+mask", "head||M", "dgrad2+wgrad1", "row store"]
+NAMES = ["issue+pads", "wait x+conv1", "conv2+mask", "head||M", "dgrad2+wgrad1", "row store"]
 
 
 def ev_time(fn, n):
