@@ -24,6 +24,7 @@ reference-faithful eager rows.
 """
 from __future__ import annotations
 
+import ctypes
 import gc
 import os
 import time
@@ -39,6 +40,7 @@ from ..utils.timing import warm_until_stable
 from ..data.dataset import ShardDataset
 from ..data.shards import ensure_synthetic_shards, list_shards, shard_header
 from ..models.tiny_ecg import TinyECG
+from ..ops import _lib
 from ..utils.csvio import LOCALITY_COLUMNS, LABL_COLUMNS, write_csv
 
 CONFIGS = [
@@ -66,20 +68,26 @@ class _Compute:
             self.mom = torch.zeros_like(self.flat)
             self.slab = torch.empty((B, slab_stride(2)), device=dev)
             self.loss = torch.zeros(1, device=dev)
+            # a one-step bf16 round on the batch as it lies (idx = NULL: row b); X, ldx, Y and B are set per call
+            self.round = _lib.TinyRound(params=self.flat.data_ptr(), mom=self.mom.data_ptr(),
+                                        slab=self.slab.data_ptr(), loss_acc=self.loss.data_ptr(), L=L, nc=2,
+                                        slab_stride=self.slab.shape[1], steps=1, lr=1e-2)
+            self.round_ref = ctypes.byref(self.round)
+            self.enqueue = _lib.kernels().ecg_tiny_round_enqueue
         else:
             self.opt = torch.optim.SGD(self.model.parameters(), lr=1e-2)
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor):
         if self.kind == "fused":
-            from ..ops import _lib
             x2 = x.reshape(x.shape[0], -1)
             y32 = y.to(torch.int32)
-            st = _lib.kernels().ecg_tiny_train_step(x2.data_ptr(), x2.shape[1], x2.stride(0), None, y32.data_ptr(),
-                                                    self.flat.data_ptr(), self.mom.data_ptr(), 2,
-                                                    self.slab.data_ptr(), self.slab.shape[1], x2.shape[0],
-                                                    self.loss.data_ptr(), 1e-2, 0.0, 0.0, 0, 0, None,
-                                                    _lib.stream_ptr(self.dev))
-            _lib.check(st, "ecg_tiny_train_step")
+            r = self.round
+            if x2.shape[1] != r.L:
+                raise ValueError(f"window length {x2.shape[1]} != {r.L}")
+            if x2.shape[0] > self.slab.shape[0]:
+                raise ValueError(f"batch {x2.shape[0]} larger than the slab's {self.slab.shape[0]} rows")
+            r.X, r.ldx, r.Y, r.B = x2.data_ptr(), x2.stride(0), y32.data_ptr(), x2.shape[0]
+            _lib.check(self.enqueue(self.round_ref, _lib.stream_ptr(self.dev)), "ecg_tiny_round_enqueue")
             return
         out = self.model(x)
         loss = F.cross_entropy(out, y)

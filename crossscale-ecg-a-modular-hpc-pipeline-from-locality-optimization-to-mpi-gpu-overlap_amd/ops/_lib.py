@@ -59,24 +59,28 @@ def _sig(lib, name, argtypes, restype=i32):
     return fn
 
 
+class TinyRound(C.Structure):
+    """``EcgTinyRound`` of csrc/kernels/tiny_ecg_step.hip, field for field (a null pointer is ``None``)."""
+    _fields_ = [("X", vp), ("ldx", i64), ("idx", vp), ("Y", vp), ("params", vp), ("mom", vp), ("slab", vp),
+                ("loss_acc", vp), ("wprep", vp), ("xg", vp), ("yg", vp),
+                ("L", i32), ("nc", i32), ("slab_stride", i32), ("B", i32), ("steps", i32),
+                ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32)]
+
+
 def _bind_kernels(lib: C.CDLL) -> None:
     _sig(lib, "ecg_tiny_param_count", [i32])
     _sig(lib, "ecg_tiny_smem_bytes", [i32, i32])
     _sig(lib, "ecg_tiny_step_grads", [vp, i32, i64, vp, vp, vp, i32, vp, i32, i32, f32, i32, vp, vp])
     _sig(lib, "ecg_tiny_forward", [vp, i32, i64, vp, vp, i32, vp, i32, i32, vp, vp])
     _sig(lib, "ecg_tiny_wprep_bytes", [])
-    _sig(lib, "ecg_tiny_train_step_pf", [vp, i32, i64, vp, vp, vp, vp, i32, vp, i32, i32, vp, f32, f32, f32, i32,
-                                         vp, i32, vp])
-    _sig(lib, "ecg_tiny_train_steps_pf", [vp, i32, i64, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, f32, f32, f32,
-                                          i32, vp, i32, vp])
     _sig(lib, "ecg_tiny_prep", [vp, vp, vp])
     _sig(lib, "ecg_slab_reduce_sgd", [vp, i32, i32, i32, vp, vp, vp, vp, f32, f32, f32, i32, i32, vp, vp])
-    _sig(lib, "ecg_tiny_train_step", [vp, i32, i64, vp, vp, vp, vp, i32, vp, i32, i32, vp, f32, f32, f32, i32,
-                                      i32, vp, vp])
-    _sig(lib, "ecg_round_graph_create", [C.POINTER(vp), vp, i32, i64, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp,
-                                         f32, f32, f32, i32, i32, vp, vp])
-    _sig(lib, "ecg_round_graph_create_pf", [C.POINTER(vp), vp, i32, i64, vp, vp, vp, vp, i32, vp, i32, i32, i32,
-                                            vp, f32, f32, f32, i32, vp, i32, i32, vp, vp])
+    native = _sig(lib, "ecg_tiny_round_sizeof", [])()
+    if native != C.sizeof(TinyRound):
+        raise NativeError(f"EcgTinyRound is {native} bytes in libecg_kernels.so but {C.sizeof(TinyRound)} in "
+                          "ops/_lib.py: rebuild the library (python csrc/build.py) or update TinyRound")
+    _sig(lib, "ecg_tiny_round_enqueue", [C.POINTER(TinyRound), vp])
+    _sig(lib, "ecg_tiny_round_capture", [C.POINTER(vp), C.POINTER(TinyRound)])
     _sig(lib, "ecg_tiny_gather_floats", [i32, i32], i64)
     _sig(lib, "ecg_tiny_step_grads_twice", [vp, i32, i64, vp, vp, vp, i32, vp, i32, i32, f32, i32, vp, vp])
     _sig(lib, "ecg_tiny_force_waves", [i32])

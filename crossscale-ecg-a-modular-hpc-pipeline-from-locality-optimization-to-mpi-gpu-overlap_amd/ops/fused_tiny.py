@@ -34,32 +34,19 @@ def prec_id(precision: str) -> int:
     return PRECISION[precision]
 
 
-def prefrag_default() -> bool:
-    """Prepared fragments (PF) on by default (``prefrag=False`` builds the conv operands in LDS every step: both
-    paths are bitwise identical, csrc/kernels/tiny_ecg_step.hip WP_* comment)."""
-    return True
-
-
 def new_wprep(device) -> torch.Tensor:
     """Device buffer for the prepared-fragment image (bf16 conv operands of the flat weights, MFMA lane order).
     Zero-initialised: the K-padding slots are never written by the SGD epilogue that keeps the image current."""
     return torch.zeros(_lib.kernels().ecg_tiny_wprep_bytes(), dtype=torch.uint8, device=device)
 
 
-def _wprep_ptr(precision: str, prefrag: Optional[bool], device, wprep: Optional[torch.Tensor] = None):
-    if precision != "bf16" or not (prefrag_default() if prefrag is None else prefrag):
+def _wprep_ptr(precision: str, prefrag: bool, device, wprep: Optional[torch.Tensor] = None):
+    """Prepared fragments (PF) are the bf16 default; ``prefrag=False`` builds the conv operands in LDS every step.
+    Both paths are bitwise identical (csrc/kernels/tiny_ecg_step.hip WP_* comment)."""
+    if precision != "bf16" or not prefrag:
         return None, None
     w = new_wprep(device) if wprep is None else wprep
     return w.data_ptr(), w
-
-
-def gather_default() -> bool:
-    """PF round graphs gather every step's windows and labels into a contiguous ping-pong buffer inside the
-    previous step's reduce launch (on by default; the ``gather`` attribute of a trainer), so the step kernel reads row b without the
-    dependent idx -> window load (csrc/kernels/tiny_ecg_step.hip GatherArgs).  Measured: step kernel 7.76 -> 7.52
-    us and step period 12.35 -> 12.08 us under the kernel tracer (medians of 687 steps), bench K=500 11.17 -> 11.06
-    us/step (profiles/r3/tiny_gather_ab.txt)."""
-    return True
 
 
 def slab_stride(num_classes: int) -> int:
@@ -90,9 +77,9 @@ def labels_int32(y: torch.Tensor, num_classes: int) -> torch.Tensor:
 
 
 def tiny_forward(flat_params: torch.Tensor, x: torch.Tensor, idx: Optional[torch.Tensor], batch: int,
-                 num_classes: int = 2, precision: str = "bf16", prefrag: Optional[bool] = None) -> torch.Tensor:
+                 num_classes: int = 2, precision: str = "bf16", prefrag: bool = True) -> torch.Tensor:
     """Logits [batch, C] of TinyECG for windows ``x[idx[b]]`` (or ``x[b]`` when idx is None).  ``prefrag``: build
-    the prepared-fragment image first and run the PF kernel (default: ``prefrag_default()``)."""
+    the prepared-fragment image first and run the PF kernel (bf16 only)."""
     _check_dataset(x, None, num_classes)
     if idx is not None:
         _check_idx(idx, batch, x.shape[0], x.device)
@@ -109,7 +96,7 @@ def tiny_forward(flat_params: torch.Tensor, x: torch.Tensor, idx: Optional[torch
 
 def tiny_step_grads(flat_params: torch.Tensor, x: torch.Tensor, y32: torch.Tensor, idx: Optional[torch.Tensor],
                     batch: int, num_classes: int = 2, slab: Optional[torch.Tensor] = None,
-                    precision: str = "bf16", prefrag: Optional[bool] = None,
+                    precision: str = "bf16", prefrag: bool = True,
                     wprep: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-sample gradient slab [batch, stride] (loss in column P) of one fused step (no update).  ``prefrag``:
     rebuild the prepared-fragment image (``wprep``, or a temporary) from the weights and run the PF kernel."""
@@ -145,12 +132,20 @@ class FusedTinyTrainer:
 
     ``model`` is flattened in place: its parameters become views of ``self.params`` so that
     ``state_dict()`` / FedAvg collectives operate on the very buffer the kernels update.
+
+    ``prefrag`` / ``gather`` (bf16 only): prepared fragments - a round's first step builds its conv operands in LDS
+    (the weights may have been rewritten since: FedAvg, broadcast, checkpoint) and its SGD epilogue rewrites the
+    whole image, which every later step of the round reads; ``gather`` (needs ``prefrag``) - every step's windows
+    and labels are gathered into a contiguous ping-pong buffer inside the previous step's reduce launch, so the
+    step kernel reads row b without the dependent idx -> window load (csrc/kernels/tiny_ecg_step.hip GatherArgs).
+    Measured: step kernel 7.76 -> 7.52 us and step period 12.35 -> 12.08 us under the kernel tracer (medians of
+    687 steps), bench K=500 11.17 -> 11.06 us/step (profiles/r3/tiny_gather_ab.txt).
     """
 
     def __init__(self, model: TinyECG, x_gpu: torch.Tensor, y_gpu: torch.Tensor, batch_size: int,
                  steps_per_round: int, lr: float = 1e-2, momentum: float = 0.9, weight_decay: float = 0.0,
                  nesterov: bool = False, seed: Optional[int] = None, use_graph: Optional[bool] = None,
-                 precision: str = "bf16", prefrag: Optional[bool] = None):
+                 precision: str = "bf16", prefrag: bool = True, gather: bool = True):
         self.device = x_gpu.device
         self.precision = precision
         self.prec = prec_id(precision)
@@ -170,87 +165,54 @@ class FusedTinyTrainer:
         self.mom = torch.zeros_like(self.params)
         self.slab = torch.empty((self.B, self.stride), dtype=torch.float32, device=self.device)
         self.loss_acc = torch.zeros(1, dtype=torch.float32, device=self.device)
+        # batches of the NEXT round are drawn into idx_stage while the current round computes; a round reads the
+        # staged table in place and the two tables then swap, so idx_table holds what the last round read
         self.idx_table = torch.zeros((self.S, self.B), dtype=torch.int32, device=self.device)
-        # batches of the NEXT round are drawn into idx_stage while the current round computes; each round graph
-        # starts with a device copy idx_stage -> idx_table (csrc capture_round)
         self.idx_stage = torch.zeros((self.S, self.B), dtype=torch.int32, device=self.device)
         self._staged: Optional[int] = None  # rows staged for the next round (None: nothing staged)
+        self._loss_steps = 0  # steps accumulated in loss_acc since its last reset
         self.sampler = DeviceIndexSampler(self.x.shape[0], self.B, self.device, seed=seed)
         # a round = one hipGraph replay, or (ECG_TINY_GRAPH=0) the same kernels enqueued from a C++ loop
         self.use_graph = (os.environ.get("ECG_TINY_GRAPH", "1") != "0") if use_graph is None else bool(use_graph)
-        self._graphs = {}  # n_steps -> native hipGraphExec handle
+        self._graphs = {}  # (n_steps, table pointer) -> native hipGraphExec handle
         self.steps_done = 0
         lib = _lib.kernels()
-        smem = lib.ecg_tiny_smem_bytes(self.x.shape[1], self.prec)
+        L = self.x.shape[1]
+        smem = lib.ecg_tiny_smem_bytes(L, self.prec)
         if smem > 160 * 1024:
-            raise ValueError(f"window length {self.x.shape[1]} too long for the fused kernel ({smem} B LDS)")
-        # prepared fragments (two-launch bf16 steps): a round's first step runs on the LDS path (the weights may
-        # have been rewritten since: FedAvg, broadcast, checkpoint) and its SGD epilogue rewrites the whole image;
-        # every later step of the round reads it
-        pf = prefrag_default() if prefrag is None else bool(prefrag)
-        self.prefrag = pf and precision == "bf16"
+            raise ValueError(f"window length {L} too long for the fused kernel ({smem} B LDS)")
+        self.prefrag = bool(prefrag) and precision == "bf16"
         self.wprep = new_wprep(self.device) if self.prefrag else None
-        self.gather = gather_default() if self.prefrag else False
+        self.gather = bool(gather) and self.prefrag
         self.xg = self.yg = None
         if self.gather:
-            self.xg = torch.zeros(lib.ecg_tiny_gather_floats(self.x.shape[1], self.B), dtype=torch.float32,
-                                  device=self.device)
+            self.xg = torch.zeros(lib.ecg_tiny_gather_floats(L, self.B), dtype=torch.float32, device=self.device)
             self.yg = torch.zeros(2 * self.B, dtype=torch.int32, device=self.device)
+        # the native description of a round; ``idx`` and ``steps`` are set per round (_round_of)
+        self._round = _lib.TinyRound(
+            X=self.x.data_ptr(), ldx=self.x.stride(0), Y=self.y32.data_ptr(), params=self.params.data_ptr(),
+            mom=self.mom.data_ptr(), slab=self.slab.data_ptr(), loss_acc=self.loss_acc.data_ptr(),
+            wprep=_lib.ptr(self.wprep), xg=_lib.ptr(self.xg), yg=_lib.ptr(self.yg), L=L, nc=self.nc,
+            slab_stride=self.stride, B=self.B, lr=self.lr, momentum=self.momentum, wd=self.wd,
+            nesterov=int(self.nesterov), prec=self.prec)
 
     # ------------------------------------------------------------------ graph management
-    def _graph_for(self, n: int) -> C.c_void_p:
-        # PF rounds read the staged table in place (no copy node) and the two index buffers swap roles after every
-        # launch, so there is one graph per (size, buffer)
-        key = (n, self.idx_stage.data_ptr()) if self.prefrag else n
+    def _round_of(self, n: int, table: torch.Tensor):
+        r = self._round
+        r.idx, r.steps = table.data_ptr(), n
+        return C.byref(r)
+
+    def _graph_for(self, n: int, table: torch.Tensor) -> C.c_void_p:
+        """Graph of an n-step round reading ``table`` in place (one per size and index buffer)."""
+        key = (n, table.data_ptr())
         g = self._graphs.get(key)
-        if g is not None:
-            return g
-        g = C.c_void_p()
-        lib = _lib.kernels()
-        torch.cuda.synchronize(self.device)
-        if self.prefrag and self.gather:
-            return self._part_graph(n, 0, key)
-        else:
-            tab, stage = (self.idx_stage, None) if self.prefrag else (self.idx_table, self.idx_stage)
-            st = lib.ecg_round_graph_create(C.byref(g), self.x.data_ptr(), self.x.shape[1], self.x.stride(0),
-                                            tab.data_ptr(), self.y32.data_ptr(), self.params.data_ptr(),
-                                            self.mom.data_ptr(), self.nc, self.slab.data_ptr(), self.stride, self.B,
-                                            n, self.loss_acc.data_ptr(), self.lr, self.momentum, self.wd,
-                                            int(self.nesterov), self.prec,
-                                            _lib.ptr(stage), _lib.ptr(self.wprep))
-        _lib.check(st, "ecg_round_graph_create")
-        self._graphs[key] = g
+        if g is None:
+            g = C.c_void_p()
+            torch.cuda.synchronize(self.device)
+            _lib.check(_lib.kernels().ecg_tiny_round_capture(C.byref(g), self._round_of(n, table)),
+                       "ecg_tiny_round_capture")
+            self._graphs[key] = g
         return g
-
-    def _part_graph(self, n: int, offset: int, key=None) -> C.c_void_p:
-        """Graph of steps [offset, offset + n) of a PF round (offset 0: it runs the image-rebuilding first step),
-        with the next-step gather when ``self.gather``."""
-        key = key or ("part", n, offset, self.idx_stage.data_ptr())
-        g = self._graphs.get(key)
-        if g is not None:
-            return g
-        g = C.c_void_p()
-        torch.cuda.synchronize(self.device)
-        st = _lib.kernels().ecg_round_graph_create_pf(
-            C.byref(g), self.x.data_ptr(), self.x.shape[1], self.x.stride(0), self.idx_stage.data_ptr(),
-            self.y32.data_ptr(), self.params.data_ptr(), self.mom.data_ptr(), self.nc, self.slab.data_ptr(), self.stride,
-            self.B, n, self.loss_acc.data_ptr(), self.lr, self.momentum, self.wd, int(self.nesterov),
-            self.wprep.data_ptr(), offset, int(offset > 0), _lib.ptr(self.xg), _lib.ptr(self.yg))
-        _lib.check(st, "ecg_round_graph_create_pf")
-        self._graphs[key] = g
-        return g
-
-    def _round_graphs(self, n: int):
-        """The graphs one replay of an n-step round launches, in order (one graph: a round split into a short head
-        graph + the tail graph, so the GPU starts while the runtime still submits the tail, measured slower at
-        every split - K=20: 11.8-12.0 vs 12.0-12.2 us/step, K=500: 10.89 vs 11.20, profiles/r3/
-        tiny_head_split_ab.txt - and was removed)."""
-        return [self._graph_for(n)]
-
-    def _swap_tables(self) -> None:
-        """After a PF graph launch: the buffer it read becomes ``idx_table`` (the last round's batches), the other
-        one receives the next staging (enqueued behind the replay on the same stream)."""
-        self.idx_table, self.idx_stage = self.idx_stage, self.idx_table
 
     def close(self):
         graphs, self._graphs = getattr(self, "_graphs", {}), {}
@@ -265,29 +227,11 @@ class FusedTinyTrainer:
             pass
 
     # ------------------------------------------------------------------ execution
-    def _eager_step(self, s: int):
-        lib = _lib.kernels()
-        if self.prefrag:
-            st = lib.ecg_tiny_train_step_pf(self.x.data_ptr(), self.x.shape[1], self.x.stride(0),
-                                            self.idx_table[s].data_ptr(), self.y32.data_ptr(), self.params.data_ptr(),
-                                            self.mom.data_ptr(), self.nc, self.slab.data_ptr(), self.stride, self.B,
-                                            self.loss_acc.data_ptr(), self.lr, self.momentum, self.wd,
-                                            int(self.nesterov), self.wprep.data_ptr(), int(s > 0),
-                                            _lib.stream_ptr(self.device))
-            _lib.check(st, "ecg_tiny_train_step_pf")
-            return
-        st = lib.ecg_tiny_train_step(self.x.data_ptr(), self.x.shape[1], self.x.stride(0),
-                                     self.idx_table[s].data_ptr(), self.y32.data_ptr(), self.params.data_ptr(),
-                                     self.mom.data_ptr(), self.nc, self.slab.data_ptr(), self.stride, self.B,
-                                     self.loss_acc.data_ptr(), self.lr, self.momentum, self.wd, int(self.nesterov),
-                                     self.prec, _lib.ptr(self.wprep),
-                                     _lib.stream_ptr(self.device))
-        _lib.check(st, "ecg_tiny_train_step")
-
     def prepare(self, sizes) -> None:
         """Draw the sampler's first permutation block, then capture, upload and warm every round graph whose step
-        count is in ``sizes``, so a later round of that size only replays.  The warm-up replay is rolled back (weights, momentum, loss, staged batches are
-        restored): it leaves the training state exactly as it found it."""
+        count is in ``sizes`` (on both index buffers), so a later round of that size only replays.  The warm-up
+        replay is rolled back (weights, momentum, loss, staged batches are restored): it leaves the training state
+        exactly as it found it."""
         self.sampler.prime()
         if not self.use_graph:
             return
@@ -297,12 +241,10 @@ class FusedTinyTrainer:
         snap = [t.clone() for t in state]
         stream = _lib.stream_ptr(self.device)
         for n in sizes:
-            for _ in range(2 if self.prefrag else 1):  # PF: both index buffers
-                for g in self._round_graphs(n):
-                    _lib.check(lib.ecg_round_graph_upload(g, stream), "ecg_round_graph_upload")
-                    _lib.check(lib.ecg_round_graph_launch(g, stream), "ecg_round_graph_launch")
-                if self.prefrag:
-                    self._swap_tables()
+            for table in (self.idx_stage, self.idx_table):
+                g = self._graph_for(n, table)
+                _lib.check(lib.ecg_round_graph_upload(g, stream), "ecg_round_graph_upload")
+                _lib.check(lib.ecg_round_graph_launch(g, stream), "ecg_round_graph_launch")
         for t, v in zip(state, snap):
             t.copy_(v)
         torch.cuda.synchronize(self.device)
@@ -315,7 +257,7 @@ class FusedTinyTrainer:
 
     def stage(self, n_steps: Optional[int] = None) -> None:
         """Draw the next round's ``n_steps`` batches into the staging table (enqueued on the current stream: it
-        runs after the rounds already enqueued, which read the staging table at their start)."""
+        runs after the rounds already enqueued, none of which reads this table)."""
         n = self._check_n(n_steps)
         self.sampler.fill(self.idx_stage[:n])
         self._staged = n
@@ -332,6 +274,19 @@ class FusedTinyTrainer:
                 raise RuntimeError(f"{self._staged} rows are staged for the next round, not {n}")
             self.stage(n)
 
+    def take_staged(self, n_steps: Optional[int] = None) -> torch.Tensor:
+        """Consume the batches staged for an ``n_steps`` round and count its steps: returns the table whose first
+        ``n_steps`` rows the round reads in place.  The two tables swap: that table is now ``idx_table`` and the
+        other one receives the next staging."""
+        n = self._check_n(n_steps)
+        if self._staged != n:
+            raise RuntimeError("launch_round without prepare_round: no batches staged for this round")
+        self._staged = None
+        self.idx_table, self.idx_stage = self.idx_stage, self.idx_table
+        self.steps_done += n
+        self._loss_steps += n
+        return self.idx_table
+
     def run_round(self, n_steps: Optional[int] = None, reset_loss: bool = True, next_n: Optional[int] = None) -> None:
         """Enqueue ``n_steps`` (default ``steps_per_round``) local SGD steps on the current stream (async);
         ``next_n``: also stage the following round's batches behind this round."""
@@ -339,36 +294,23 @@ class FusedTinyTrainer:
         self.launch_round(n_steps, next_n)
 
     def launch_round(self, n_steps: Optional[int] = None, next_n: Optional[int] = None) -> None:
-        """The round's SGD steps on the staged batches (one graph replay), then optionally stage the next round."""
+        """The round's SGD steps on the staged batches (one graph replay, or the same launches enqueued one by
+        one), then optionally stage the next round."""
         n = self._check_n(n_steps)
-        if self._staged != n:
-            raise RuntimeError("launch_round without prepare_round: no batches staged for this round")
-        self._staged = None
+        table = self.take_staged(n)
+        stream = _lib.stream_ptr(self.device)
         if self.use_graph:
-            stream = _lib.stream_ptr(self.device)
-            for g in self._round_graphs(n):
-                _lib.check(_lib.kernels().ecg_round_graph_launch(g, stream), "ecg_round_graph_launch")
-            if self.prefrag:
-                self._swap_tables()
-        elif self.prefrag:  # the graph's kernels enqueued from one C++ loop, reading the staged table in place
-            _lib.check(_lib.kernels().ecg_tiny_train_steps_pf(
-                self.x.data_ptr(), self.x.shape[1], self.x.stride(0), self.idx_stage.data_ptr(), self.y32.data_ptr(),
-                self.params.data_ptr(), self.mom.data_ptr(), self.nc, self.slab.data_ptr(), self.stride, self.B, n,
-                self.loss_acc.data_ptr(), self.lr, self.momentum, self.wd, int(self.nesterov),
-                self.wprep.data_ptr(), 0, _lib.stream_ptr(self.device)), "ecg_tiny_train_steps_pf")
-            self._swap_tables()
+            _lib.check(_lib.kernels().ecg_round_graph_launch(self._graph_for(n, table), stream),
+                       "ecg_round_graph_launch")
         else:
-            self.idx_table[:n].copy_(self.idx_stage[:n])
-            for s in range(n):
-                self._eager_step(s)
-        self.steps_done += n
-        self._loss_steps = getattr(self, "_loss_steps", 0) + n
+            _lib.check(_lib.kernels().ecg_tiny_round_enqueue(self._round_of(n, table), stream),
+                       "ecg_tiny_round_enqueue")
         if next_n is not None:
             self.stage(next_n)
 
     def avg_loss(self) -> float:
         """Mean per-step loss since the last reset (synchronises)."""
-        return float(self.loss_acc.item()) / (self.B * max(1, getattr(self, "_loss_steps", self.S)))
+        return float(self.loss_acc.item()) / (self.B * max(1, self._loss_steps))
 
     def reset_momentum(self):
         self.mom.zero_()

@@ -135,14 +135,11 @@ def _ddp_fused_round(trainer, ctx: DistContext, n: int):
     if not hasattr(trainer, "_ddp_opt"):
         trainer._ddp_grad = torch.zeros_like(trainer.params)
         trainer._ddp_opt = FlatSGD(trainer.params, trainer._ddp_grad, lr=trainer.lr, momentum=trainer.momentum)
-    trainer._loss_steps = n  # batches already drawn by trainer.prepare_round(n) into the staging table
-    trainer.idx_table[:n].copy_(trainer.idx_stage[:n])
-    trainer._staged = None
+    table = trainer.take_staged(n)  # batches already drawn by trainer.prepare_round(n)
     lib = _lib.kernels()
     for s in range(n):
-        tiny_step_grads(trainer.params, trainer.x, trainer.y32, trainer.idx_table[s], trainer.B, trainer.nc,
-                        trainer.slab, precision=trainer.precision, prefrag=getattr(trainer, "prefrag", None),
-                        wprep=getattr(trainer, "wprep", None))
+        tiny_step_grads(trainer.params, trainer.x, trainer.y32, table[s], trainer.B, trainer.nc, trainer.slab,
+                        precision=trainer.precision, prefrag=trainer.prefrag, wprep=trainer.wprep)
         st = lib.ecg_slab_reduce_sgd(trainer.slab.data_ptr(), trainer.B, trainer.stride, trainer.P, None, None,
                                      trainer._ddp_grad.data_ptr(), trainer.loss_acc.data_ptr(), 0.0, 0.0, 0.0, 0, 0,
                                      None, _lib.stream_ptr(trainer.device))

@@ -106,13 +106,14 @@ constexpr int F32_KSTEPS = C * K2 / 4;
 //   WP_FRAGD  bf16 [3][64][8]  conv2 dgrad operand     (element (r, ci), r = 16k + co)
 //   WP_AW1    bf16 [16][8]     conv1 A operand row c: {w1[c][0..6], b1[c]}
 //   WP_B2     fp32 [16]        conv2 bias (byte offset WP_B2_BYTE)
-// tiny_prep_kernel writes the whole image from the flat parameters (the first node of every round graph: a
-// FedAvg all-reduce / broadcast / checkpoint load may have rewritten the weights between rounds), and
-// slab_reduce_sgd_kernel's SGD epilogue rewrites each updated parameter's slots, so inside a round the image
-// always equals what put_param would have built from ``params``: bitwise the same MFMA operands.  Every step
-// workgroup then loads its operands straight into VGPRs (7 x 16 B per lane, L2-hot: all 32 workgroups of an
-// XCD read the same 6.4 KB): no per-step scatter into LDS (1,280 x 2 two-byte stores + conversions per sample)
-// and no LDS round trip for the fragments in conv1 / conv2 / dgrad.
+// tiny_prep_kernel writes the whole image from the flat parameters (ecg_tiny_prep and the gradient-only / forward
+// entry points), and slab_reduce_sgd_kernel's SGD epilogue rewrites each updated parameter's slots.  A round has
+// no prep launch: a FedAvg all-reduce / broadcast / checkpoint load may have rewritten the weights since the last
+// one, so its first step builds its operands in LDS and that step's SGD epilogue rewrites the whole image.  From
+// then on the image equals what put_param would have built from ``params`` - bitwise the same MFMA operands - and
+// every step workgroup loads its operands straight into VGPRs (7 x 16 B per lane, L2-hot: all 32 workgroups of
+// an XCD read the same 6.4 KB): no per-step scatter into LDS (1,280 x 2 two-byte stores + conversions per
+// sample) and no LDS round trip for the fragments in conv1 / conv2 / dgrad.
 constexpr int WP_FRAGF = 0;
 constexpr int WP_FRAGD = 3 * 64 * 8;
 constexpr int WP_AW1 = 2 * 3 * 64 * 8;
@@ -147,24 +148,16 @@ __device__ __forceinline__ void wprep_put(unsigned char* wp, int i, float v) {
   }
 }
 
-// Block 0: the whole prepared-fragment image from ``params`` (K padding rows r in [80, 96) zero).  Blocks 1..:
-// optional int32 copy idx_src -> idx_dst (n ints; the round graph's staged batch rows), 4 KB per block.
+// One block: the whole prepared-fragment image from ``params`` (K padding rows r in [80, 96) zero).
 __global__ __launch_bounds__(256) void tiny_prep_kernel(const float* __restrict__ params,
-                                                        unsigned char* __restrict__ wp,
-                                                        const int* __restrict__ idx_src, int* __restrict__ idx_dst,
-                                                        long n_idx) {
+                                                        unsigned char* __restrict__ wp) {
   const int tid = threadIdx.x;
-  if (blockIdx.x == 0) {
-    for (int i = tid; i < kParamsW2End + C; i += 256) wprep_put(wp, i, params[i]);
-    __bf16* wb = reinterpret_cast<__bf16*>(wp);
-    for (int e = tid; e < 2 * 32 * 8; e += 256) {
-      const int which = e >> 8, l = 32 + ((e >> 3) & 31), j = e & 7;
-      if (!frag_pad_is_bias(which, l, j)) wb[(which ? WP_FRAGD : WP_FRAGF) + (2 * 64 + l) * 8 + j] = ecg::to_bf16(0.f);
-    }
-    return;
+  for (int i = tid; i < kParamsW2End + C; i += 256) wprep_put(wp, i, params[i]);
+  __bf16* wb = reinterpret_cast<__bf16*>(wp);
+  for (int e = tid; e < 2 * 32 * 8; e += 256) {
+    const int which = e >> 8, l = 32 + ((e >> 3) & 31), j = e & 7;
+    if (!frag_pad_is_bias(which, l, j)) wb[(which ? WP_FRAGD : WP_FRAGF) + (2 * 64 + l) * 8 + j] = ecg::to_bf16(0.f);
   }
-  const long base = (long)(blockIdx.x - 1) * 1024;
-  for (long i = base + tid; i < n_idx && i < base + 1024; i += 256) idx_dst[i] = idx_src[i];
 }
 
 __host__ __device__ inline Smem make_smem(int L, int waves, int nc = MAX_CLASSES, bool f32 = false) {
@@ -1116,7 +1109,7 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
 constexpr int kRedColsDefault = 32;
 constexpr int RED_ROWG = 16;
 
-// Next-step gather riding on the reduce launch (ECG_TINY_GATHER): blocks >= nred copy the windows and labels of
+// Next-step gather riding on the reduce launch: blocks >= nred copy the windows and labels of
 // the NEXT step's batch (idx) into a contiguous buffer xg [B][ldg] / yg [B], so that step's kernel stages row b
 // directly - its phase 0 loses the dependent idx -> window round trip.  The reduce blocks are latency-bound
 // (46 blocks on 256 CUs), so the copy runs beside them on otherwise idle CUs instead of as a launch of its own
@@ -1210,28 +1203,46 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_sgd_kernel(
 
 unsigned long long* g_stamps = nullptr;  // diagnostic phase stamps (ecg_tiny_set_stamps)
 
+FusedOpt no_fuse() {
+  FusedOpt o{};
+  // Write-through gradient rows: the rows leave the XCD L2s while the step runs instead of in the boundary's
+  // write-back, and the reduce kernel finds them beyond L2: 11.1 vs 11.4 us/step with plain stores (bench, A/B x2,
+  // profiles/r2/bench_slab_wt.txt).
+  o.slab_wt = 1;
+  return o;
+}
+
+// One launch of the step kernel: B workgroups, workgroup b on window X[idx ? idx[b] : b].
+struct StepArgs {
+  const float* X;  // windows [N][ldx], window length L
+  int L;
+  long ldx;
+  const int* idx;  // [B] rows of X (nullptr: row b)
+  const int* Y;    // [N] labels (unused by MODE 1)
+  const float* params;
+  int nc;
+  float* out;  // MODE 0/2: slab [B][out_stride]; MODE 1: logits
+  int out_stride, B;
+  float inv_B;
+  const unsigned char* wprep;  // PF image of ``params`` (bf16 only); nullptr: operands built in LDS from ``params``
+};
 
 template <int WAVES, int MODE, bool F32, bool PF>
-int launch_step(const float* X, int L, long ldx, const int* idx, const int* Y, const float* params, int nc,
-                float* out, int out_stride, int B, float inv_B, const FusedOpt& opt, const unsigned char* wprep,
-                hipStream_t stream) {
-  const Smem sm = make_smem(L, WAVES, nc, F32);
+int launch_step(const StepArgs& a, hipStream_t stream) {
+  const Smem sm = make_smem(a.L, WAVES, a.nc, F32);
   auto kern = tiny_ecg_step_kernel<WAVES, MODE, F32, PF>;
   if (sm.bytes > 64 * 1024)
     ECG_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, sm.bytes));
-  hipLaunchKernelGGL(kern, dim3(B), dim3(WAVES * 64), sm.bytes, stream, X, L, ldx, idx, Y, params, nc, out,
-                     out_stride, inv_B, g_stamps, opt, wprep);
+  hipLaunchKernelGGL(kern, dim3(a.B), dim3(WAVES * 64), sm.bytes, stream, a.X, a.L, a.ldx, a.idx, a.Y, a.params, a.nc,
+                     a.out, a.out_stride, a.inv_B, g_stamps, no_fuse(), PF ? a.wprep : nullptr);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
 
-// The prepared-fragment image of ``params`` (+ optional idx copy), one launch.
-int launch_prep(const float* params, unsigned char* wprep, const int* idx_src, int* idx_dst, long n_idx,
-                hipStream_t stream) {
-  if (!params || !wprep || (n_idx > 0 && (!idx_src || !idx_dst))) return ecg::kBadArg;
-  const long nb = 1 + (n_idx > 0 ? (n_idx + 1023) / 1024 : 0);
-  hipLaunchKernelGGL(tiny_prep_kernel, dim3((unsigned)nb), dim3(256), 0, stream, params, wprep, idx_src, idx_dst,
-                     n_idx > 0 ? n_idx : 0);
+// The prepared-fragment image of ``params``, one launch.
+int launch_prep(const float* params, unsigned char* wprep, hipStream_t stream) {
+  if (!params || !wprep) return ecg::kBadArg;
+  hipLaunchKernelGGL(tiny_prep_kernel, dim3(1), dim3(256), 0, stream, params, wprep);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -1264,50 +1275,26 @@ int check_step_args(int L, int nc, int B, int out_stride, int mode, bool f32 = f
 }
 
 template <bool F32, bool PF>
-int dispatch_cfg(int mode, int waves, const float* X, int L, long ldx, const int* idx, const int* Y,
-                 const float* params, int nc, float* out, int out_stride, int B, float inv_B, const FusedOpt& opt,
-                 const unsigned char* wprep, hipStream_t stream) {
+int dispatch_cfg(int mode, int waves, const StepArgs& a, hipStream_t stream) {
   if (mode == 2)  // diagnostic (8 waves: the 16-wave two-pass variant spills registers; the production kernel's own
                  // phase stamps come from MODE 0 with ecg_tiny_set_stamps, scripts/diag_step_phases.py)
-    return launch_step<8, 2, F32, PF>(X, L, ldx, idx, Y, params, nc, out, out_stride, B, inv_B, opt, wprep, stream);
-  if (mode == 0)
-    return waves == 8
-               ? launch_step<8, 0, F32, PF>(X, L, ldx, idx, Y, params, nc, out, out_stride, B, inv_B, opt, wprep, stream)
-               : launch_step<16, 0, F32, PF>(X, L, ldx, idx, Y, params, nc, out, out_stride, B, inv_B, opt, wprep,
-                                             stream);
-  return waves == 8
-             ? launch_step<8, 1, F32, PF>(X, L, ldx, idx, Y, params, nc, out, out_stride, B, inv_B, opt, wprep, stream)
-             : launch_step<16, 1, F32, PF>(X, L, ldx, idx, Y, params, nc, out, out_stride, B, inv_B, opt, wprep, stream);
+    return launch_step<8, 2, F32, PF>(a, stream);
+  if (mode == 0) return waves == 8 ? launch_step<8, 0, F32, PF>(a, stream) : launch_step<16, 0, F32, PF>(a, stream);
+  return waves == 8 ? launch_step<8, 1, F32, PF>(a, stream) : launch_step<16, 1, F32, PF>(a, stream);
 }
 
-// prec: 0 = bf16 MFMA operands (AMP), 1 = fp32 (exact f32 MFMA).  ``wprep`` (bf16 only, not with the in-kernel
-// reduction of ``opt``): the kernel reads its conv operands from that prepared-fragment image, which the caller
-// keeps equal to ``params`` (launch_prep / slab_reduce_sgd_kernel); nullptr: the in-LDS build from ``params``.
-int step_dispatch(int mode, int prec, const float* X, int L, long ldx, const int* idx, const int* Y,
-                  const float* params, int nc, float* out, int out_stride, int B, float inv_B, const FusedOpt& opt,
-                  const unsigned char* wprep, hipStream_t stream) {
+// prec: 0 = bf16 MFMA operands (AMP), 1 = fp32 (exact f32 MFMA).  ``a.wprep`` (bf16 only): the kernel reads its
+// conv operands from that prepared-fragment image, which the caller keeps equal to ``params`` (launch_prep /
+// slab_reduce_sgd_kernel); nullptr: the in-LDS build from ``params``.
+int step_dispatch(int mode, int prec, const StepArgs& a, hipStream_t stream) {
   if (prec != 0 && prec != 1) return ecg::kBadArg;
-  int st = check_step_args(L, nc, B, out_stride, mode, prec == 1);
+  int st = check_step_args(a.L, a.nc, a.B, a.out_stride, mode, prec == 1);
   if (st) return st;
-  if (wprep && prec == 1) return ecg::kBadArg;
-  const int waves = pick_waves(L, prec == 1);
-  if (prec == 1)
-    return dispatch_cfg<true, false>(mode, waves, X, L, ldx, idx, Y, params, nc, out, out_stride, B, inv_B, opt,
-                                     nullptr, stream);
-  if (wprep)
-    return dispatch_cfg<false, true>(mode, waves, X, L, ldx, idx, Y, params, nc, out, out_stride, B, inv_B, opt,
-                                     wprep, stream);
-  return dispatch_cfg<false, false>(mode, waves, X, L, ldx, idx, Y, params, nc, out, out_stride, B, inv_B, opt,
-                                    nullptr, stream);
-}
-
-FusedOpt no_fuse() {
-  FusedOpt o{};
-  // Write-through gradient rows: the rows leave the XCD L2s while the step runs instead of in the boundary's
-  // write-back, and the reduce kernel finds them beyond L2: 11.1 vs 11.4 us/step with plain stores (bench, A/B x2,
-  // profiles/r2/bench_slab_wt.txt).
-  o.slab_wt = 1;
-  return o;
+  if (a.wprep && prec == 1) return ecg::kBadArg;
+  const int waves = pick_waves(a.L, prec == 1);
+  if (prec == 1) return dispatch_cfg<true, false>(mode, waves, a, stream);
+  if (a.wprep) return dispatch_cfg<false, true>(mode, waves, a, stream);
+  return dispatch_cfg<false, false>(mode, waves, a, stream);
 }
 
 int reduce_dispatch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
@@ -1354,7 +1341,6 @@ ECG_API int ecg_tiny_set_stamps(unsigned long long* stamps) {
 // Force the per-step kernel's wave count (8 or 16; 0 = automatic); returns the previous setting.  Tests use it
 // to compare paths at the same per-sample summation order.  Graphs captured before a change keep their kernel.
 ECG_API int ecg_tiny_force_waves(int waves) {
-  pick_waves(32, false);  // resolve the environment default first
   const int prev = g_forced_waves;
   g_forced_waves = (waves == 8 || waves == 16) ? waves : 0;
   return prev;
@@ -1369,42 +1355,42 @@ ECG_API int ecg_tiny_wprep_bytes(void) { return WP_BYTES; }
 
 // Build the prepared-fragment image of ``params`` (bf16 conv operands in MFMA lane order).
 ECG_API int ecg_tiny_prep(const float* params, void* wprep, hipStream_t stream) {
-  return launch_prep(params, static_cast<unsigned char*>(wprep), nullptr, nullptr, 0, stream);
+  return launch_prep(params, static_cast<unsigned char*>(wprep), stream);
 }
 
-// Entry points below take an optional ``wprep`` (bf16 only): when given, the image is first rebuilt from
+// The three entry points below take an optional ``wprep`` (bf16 only): when given, the image is first rebuilt from
 // ``params`` (one small launch) and the step kernel reads its conv operands from it (PF path); nullptr builds
 // them in every workgroup's LDS.  Both give bitwise-identical results.
-static int prep_then(int mode, int prec, const float* X, int L, long ldx, const int* idx, const int* Y,
-                     const float* params, int nc, float* out, int out_stride, int B, float inv_B, void* wprep,
-                     hipStream_t stream) {
-  if (wprep) {
+static int prep_then(int mode, int prec, const StepArgs& a, hipStream_t stream) {
+  if (a.wprep) {
     if (prec != 0) return ecg::kBadArg;
-    const int st = launch_prep(params, static_cast<unsigned char*>(wprep), nullptr, nullptr, 0, stream);
+    const int st = launch_prep(a.params, const_cast<unsigned char*>(a.wprep), stream);
     if (st) return st;
   }
-  return step_dispatch(mode, prec, X, L, ldx, idx, Y, params, nc, out, out_stride, B, inv_B, no_fuse(),
-                       static_cast<const unsigned char*>(wprep), stream);
+  return step_dispatch(mode, prec, a, stream);
 }
 
 // One fused training step's gradient pass: writes slab[B][slab_stride] (grads + loss at column P).
 ECG_API int ecg_tiny_step_grads(const float* X, int L, long ldx, const int* idx, const int* Y,
                                 const float* params, int nc, float* slab, int slab_stride, int B, float inv_B,
                                 int prec, void* wprep, hipStream_t stream) {
-  return prep_then(0, prec, X, L, ldx, idx, Y, params, nc, slab, slab_stride, B, inv_B, wprep, stream);
+  return prep_then(0, prec, {X, L, ldx, idx, Y, params, nc, slab, slab_stride, B, inv_B,
+                             static_cast<const unsigned char*>(wprep)}, stream);
 }
 
 // Diagnostic twin of ecg_tiny_step_grads: every workgroup computes its sample twice (cold, then warm caches).
 ECG_API int ecg_tiny_step_grads_twice(const float* X, int L, long ldx, const int* idx, const int* Y,
                                       const float* params, int nc, float* slab, int slab_stride, int B, float inv_B,
                                       int prec, void* wprep, hipStream_t stream) {
-  return prep_then(2, prec, X, L, ldx, idx, Y, params, nc, slab, slab_stride, B, inv_B, wprep, stream);
+  return prep_then(2, prec, {X, L, ldx, idx, Y, params, nc, slab, slab_stride, B, inv_B,
+                             static_cast<const unsigned char*>(wprep)}, stream);
 }
 
 // Inference: logits[B][nc] for windows X[idx[b]].
 ECG_API int ecg_tiny_forward(const float* X, int L, long ldx, const int* idx, const float* params, int nc,
                              float* logits, int B, int prec, void* wprep, hipStream_t stream) {
-  return prep_then(1, prec, X, L, ldx, idx, nullptr, params, nc, logits, nc, B, 0.f, wprep, stream);
+  return prep_then(1, prec, {X, L, ldx, idx, nullptr, params, nc, logits, nc, B, 0.f,
+                             static_cast<const unsigned char*>(wprep)}, stream);
 }
 
 ECG_API int ecg_slab_reduce_sgd(const float* slab, int G, int stride, int P, float* params, float* mom,
@@ -1415,111 +1401,96 @@ ECG_API int ecg_slab_reduce_sgd(const float* slab, int G, int stride, int P, flo
                          static_cast<unsigned char*>(wprep), stream);
 }
 
-// One training step.  With a PF image ``wprep``: ``image`` 0 = rebuild it from ``params`` first (prep launch),
-// 1 = it is current (read it), 2 = it is stale - run this step's kernel on the LDS path and let its SGD epilogue
-// rewrite the whole image (every parameter slot is updated every step; the K-padding slots stay zero from the
-// zero-initialised allocation), which is how a round starts without a prep launch.
-static int train_step(const float* X, int L, long ldx, const int* idx, const int* Y, float* params, float* mom,
-                      int nc, float* slab, int slab_stride, int B, float* loss_acc, float lr, float momentum, float wd,
-                      int nesterov, int prec, unsigned char* wprep, int image, hipStream_t stream,
-                      const GatherArgs* gather = nullptr) {
-  int st = ecg::kOk;
-  if (wprep && image == 0) st = launch_prep(params, wprep, nullptr, nullptr, 0, stream);
+// A local round: ``steps`` times "step kernel, then reduce + SGD kernel".  ops/_lib.py mirrors this struct field
+// for field and compares its size with ecg_tiny_round_sizeof() when it binds the library.
+struct EcgTinyRound {
+  const float* X;  // dataset windows [N][ldx], window length L
+  long ldx;
+  const int* idx;  // [steps][B] batch rows, read in place; nullptr: every step reads rows 0..B-1
+  const int* Y;    // [N] int32 labels
+  float* params;   // flat fp32 weights [P], updated in place
+  float* mom;      // [P] (may be null when momentum == 0)
+  float* slab;     // [B][slab_stride] gradient rows (scratch)
+  float* loss_acc;  // [1] += the summed sample losses of every step (nullable)
+  void* wprep;  // PF image (bf16 only, nullable).  The first step builds its operands in LDS - the weights may have
+                // been rewritten since the last round - and its SGD epilogue rewrites the image; later steps read it.
+  float* xg;    // [2][B][ldg] / yg [2][B] (both or neither; need wprep and idx): the reduce launch of step s
+  int* yg;      // gathers step s + 1's windows and labels into buffer (s + 1) & 1, which that step reads by row
+  int L, nc, slab_stride, B, steps;
+  float lr, momentum, wd;
+  int nesterov, prec;
+};
+
+ECG_API int ecg_tiny_round_sizeof(void) { return (int)sizeof(EcgTinyRound); }
+
+static int check_round(const EcgTinyRound* r) {
+  if (!r || r->steps < 1 || !r->X || !r->Y || !r->params || !r->slab) return ecg::kBadArg;
+  if (r->prec != 0 && r->prec != 1) return ecg::kBadArg;
+  if (r->wprep && r->prec != 0) return ecg::kBadArg;
+  if ((!r->xg) != (!r->yg) || (r->xg && (!r->wprep || !r->idx))) return ecg::kBadArg;
+  return check_step_args(r->L, r->nc, r->B, r->slab_stride, 0, r->prec == 1);
+}
+
+// Enqueue a checked round on ``stream`` (a capturing stream included): two launches per step.
+// (Warm-up loads of the next step's windows in the step kernel's tail measured neutral - 11.11 vs 11.08 us/step,
+// the windows already sit in the Infinity Cache; profiles/r2/bench_prefetch.txt - and were removed.)
+static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
+  const int P = make_layout(r.nc).P;
+  unsigned char* wprep = static_cast<unsigned char*>(r.wprep);
+  // Gathered steps (xg/yg): step s > 0 reads ping-pong buffer s & 1, which the reduce launch of step s - 1 filled
+  // (stream order: that buffer's previous reader, step s - 2's kernel, finished before that reduce started).
+  const int ldg = (r.L + 3) / 4 * 4;
+  GatherArgs ga{r.X, r.ldx, nullptr, r.Y, nullptr, nullptr, r.L, ldg, r.B,
+                (r.L % 4 == 0 && r.ldx % 4 == 0 && reinterpret_cast<uintptr_t>(r.X) % 16 == 0) ? 1 : 0, INT_MAX};
+  for (int s = 0; s < r.steps; ++s) {
+    const int* idx = r.idx ? r.idx + (long)s * r.B : nullptr;
+    const bool gathered = r.xg && s > 0;
+    const bool gather_next = r.xg && s + 1 < r.steps;
+    if (gather_next) {
+      ga.idx = idx + r.B;
+      ga.xg = r.xg + (long)((s + 1) & 1) * r.B * ldg;
+      ga.yg = r.yg + (long)((s + 1) & 1) * r.B;
+    }
+    StepArgs a{r.X, r.L, r.ldx, idx, r.Y, r.params, r.nc, r.slab, r.slab_stride, r.B, 1.0f / (float)r.B,
+               s == 0 ? nullptr : wprep};
+    if (gathered) {
+      a.X = r.xg + (long)(s & 1) * r.B * ldg;
+      a.ldx = ldg;
+      a.idx = nullptr;
+      a.Y = r.yg + (long)(s & 1) * r.B;
+    }
+    int st = step_dispatch(0, r.prec, a, stream);
+    if (st) return st;
+    st = reduce_dispatch(r.slab, r.B, r.slab_stride, P, r.params, r.mom, nullptr, r.loss_acc, r.lr, r.momentum, r.wd,
+                         r.nesterov, 1, wprep, stream, gather_next ? &ga : nullptr);
+    if (st) return st;
+  }
+  return ecg::kOk;
+}
+
+// The round's kernels enqueued on ``stream``, without a graph.
+ECG_API int ecg_tiny_round_enqueue(const EcgTinyRound* round, hipStream_t stream) {
+  const int st = check_round(round);
+  return st ? st : enqueue_round(*round, stream);
+}
+
+// The same launches captured into one hipGraph (replayed by ecg_round_graph_launch).  All pointers are baked
+// into the graph: callers keep the buffers alive and refill ``idx`` in place.
+ECG_API int ecg_tiny_round_capture(void** handle, const EcgTinyRound* round) {
+  if (!handle) return ecg::kBadArg;
+  int st = check_round(round);
   if (st) return st;
-  FusedOpt o = no_fuse();
-  // (Warm-up loads of the next step's windows in the step kernel's tail measured neutral - 11.11 vs 11.08 us/step,
-  // the windows already sit in the Infinity Cache; profiles/r2/bench_prefetch.txt - and were removed.)
-  st = step_dispatch(0, prec, X, L, ldx, idx, Y, params, nc, slab, slab_stride, B, 1.0f / (float)B, o,
-                     image == 2 ? nullptr : wprep, stream);
-  if (st) return st;
-  return reduce_dispatch(slab, B, slab_stride, make_layout(nc).P, params, mom, nullptr, loss_acc, lr, momentum, wd,
-                         nesterov, 1, wprep, stream, gather);
-}
-
-// Full training step: two launches (gradient slab, then slab_reduce_sgd_kernel) - three with ``wprep`` (the PF
-// image is rebuilt first).
-ECG_API int ecg_tiny_train_step(const float* X, int L, long ldx, const int* idx, const int* Y, float* params,
-                                float* mom, int nc, float* slab, int slab_stride, int B, float* loss_acc, float lr,
-                                float momentum, float wd, int nesterov, int prec, void* wprep, hipStream_t stream) {
-  return train_step(X, L, ldx, idx, Y, params, mom, nc, slab, slab_stride, B, loss_acc, lr, momentum, wd, nesterov,
-                    prec, static_cast<unsigned char*>(wprep), 0, stream);
-}
-
-// Two-launch training step that keeps a zero-initialised PF image current without prep launches: ``image_current``
-// 0 runs the LDS-path kernel (e.g. the first step after the weights were changed outside the step loop) and its
-// SGD epilogue rewrites the whole image; 1 reads the image (every later step).
-ECG_API int ecg_tiny_train_step_pf(const float* X, int L, long ldx, const int* idx, const int* Y, float* params,
-                                   float* mom, int nc, float* slab, int slab_stride, int B, float* loss_acc, float lr,
-                                   float momentum, float wd, int nesterov, void* wprep, int image_current,
-                                   hipStream_t stream) {
-  if (!wprep) return ecg::kBadArg;
-  return train_step(X, L, ldx, idx, Y, params, mom, nc, slab, slab_stride, B, loss_acc, lr, momentum, wd, nesterov,
-                    0, static_cast<unsigned char*>(wprep), image_current ? 1 : 2, stream);
-}
-
-// ``steps`` two-launch PF steps (batch s reads idx_table + s*B) enqueued directly from C++: the same kernels and
-// order as a round graph replay (first step on the LDS path unless ``image_current``), without the graph launch.
-ECG_API int ecg_tiny_train_steps_pf(const float* X, int L, long ldx, const int* idx_table, const int* Y,
-                                    float* params, float* mom, int nc, float* slab, int slab_stride, int B, int steps,
-                                    float* loss_acc, float lr, float momentum, float wd, int nesterov, void* wprep,
-                                    int image_current, hipStream_t stream) {
-  if (!wprep || steps < 1) return ecg::kBadArg;
-  int st = ecg::kOk;
-  for (int s = 0; s < steps && st == 0; ++s)
-    st = train_step(X, L, ldx, idx_table + (long)s * B, Y, params, mom, nc, slab, slab_stride, B, loss_acc, lr,
-                    momentum, wd, nesterov, 0, static_cast<unsigned char*>(wprep), (s > 0 || image_current) ? 1 : 2,
-                    stream);
-  return st;
-}
-
-static int capture_round(void** handle, int steps, int prec, const float* X, int L, long ldx, const int* idx_table,
-                         const int* Y, float* params, float* mom, int nc, float* slab, int slab_stride, int B,
-                         float* loss_acc, float lr, float momentum, float wd, int nesterov, const int* idx_stage,
-                         unsigned char* wprep, int step_offset = 0, int image_current = 0, float* xg = nullptr,
-                         int* yg = nullptr) {
   hipStream_t cap;
   ECG_HIP_CHECK(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
   RoundGraph* rg = new RoundGraph();
-  rg->steps = steps;
+  rg->steps = round->steps;
   hipError_t e = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) {
     delete rg;
     (void)hipStreamDestroy(cap);
     return ecg::kHipError;
   }
-  int st = 0;
-  // Staged batches: the round's index rows were enqueued into idx_stage one round ahead (while the previous round
-  // computed); the graph's first node moves them into the table every replay reads.  The PF round needs no such
-  // node: its steps read idx_stage itself (the next round's staging is enqueued behind the replay on the same
-  // stream), and its first step runs on the LDS path, whose SGD epilogue rewrites the image for the rest.
-  const int* tab = idx_table;
-  if (wprep) {
-    if (idx_stage) tab = idx_stage;
-  } else if (idx_stage && hipMemcpyAsync(const_cast<int*>(idx_table), idx_stage, (size_t)steps * B * sizeof(int),
-                                         hipMemcpyDeviceToDevice, cap) != hipSuccess) {
-    st = ecg::kHipError;
-  }
-  if (st == 0) {
-    // Gathered steps (xg/yg): step s > 0 reads ping-pong buffer s & 1, which the reduce launch of step s - 1 filled
-    // (stream order: that buffer's previous reader, step s - 2's kernel, finished before that reduce started).
-    const int ldg = (L + 3) / 4 * 4;
-    GatherArgs ga{X, ldx, nullptr, Y, nullptr, nullptr, L, ldg, B,
-                  (L % 4 == 0 && ldx % 4 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0) ? 1 : 0, INT_MAX};
-    for (int s = 0; s < steps && st == 0; ++s) {
-      const long row = (long)(step_offset + s) * B;
-      const bool gathered = xg && s > 0;
-      const bool gather_next = xg && s + 1 < steps;
-      if (gather_next) {
-        ga.idx = tab + row + B;
-        ga.xg = xg + (long)((s + 1) & 1) * B * ldg;
-        ga.yg = yg + (long)((s + 1) & 1) * B;
-      }
-      st = train_step(gathered ? xg + (long)(s & 1) * B * ldg : X, L, gathered ? (long)ldg : ldx,
-                      gathered ? nullptr : tab + row, gathered ? yg + (long)(s & 1) * B : Y, params, mom, nc, slab,
-                      slab_stride, B, loss_acc, lr, momentum, wd, nesterov, prec, wprep,
-                      (s == 0 && !image_current) ? 2 : 1, cap, gather_next ? &ga : nullptr);
-    }
-  }
+  st = enqueue_round(*round, cap);
   e = hipStreamEndCapture(cap, &rg->graph);
   (void)hipStreamDestroy(cap);
   if (st != 0 || e != hipSuccess) {
@@ -1537,39 +1508,7 @@ static int capture_round(void** handle, int steps, int prec, const float* X, int
   return ecg::kOk;
 }
 
-// Capture ``steps`` consecutive fused steps (batch s reads idx_table + s*B) into one hipGraph.
-// All pointers are baked into the graph: callers keep the buffers alive and refill idx_table in place.
-// ``idx_stage`` (optional): the graph first copies idx_stage[0 : steps*B] into idx_table.  ``wprep`` (optional,
-// bf16, two-launch steps only): the PF image, rebuilt by the graph's first node and kept by every step's SGD.
-ECG_API int ecg_round_graph_create(void** handle, const float* X, int L, long ldx, const int* idx_table,
-                                   const int* Y, float* params, float* mom, int nc, float* slab, int slab_stride,
-                                   int B, int steps, float* loss_acc, float lr, float momentum, float wd,
-                                   int nesterov, int prec, const int* idx_stage, void* wprep) {
-  if (!handle || steps <= 0) return ecg::kBadArg;
-  int st = check_step_args(L, nc, B, slab_stride, 0, prec == 1);
-  if (st) return st;
-  if (wprep && prec != 0) return ecg::kBadArg;
-  return capture_round(handle, steps, prec, X, L, ldx, idx_table, Y, params, mom, nc, slab, slab_stride, B, loss_acc,
-                       lr, momentum, wd, nesterov, idx_stage, static_cast<unsigned char*>(wprep));
-}
-
-// A PF round (``ecg_round_graph_create`` with ``wprep`` and ``idx_stage``): captures steps [step_offset,
-// step_offset + steps) of the staged table; ``image_current`` = 1 when the PF image is already current (else the
-// first captured step runs on the LDS path, whose SGD epilogue rewrites the image).
-ECG_API int ecg_round_graph_create_pf(void** handle, const float* X, int L, long ldx, const int* idx_stage,
-                                      const int* Y, float* params, float* mom, int nc, float* slab, int slab_stride,
-                                      int B, int steps, float* loss_acc, float lr, float momentum, float wd,
-                                      int nesterov, void* wprep, int step_offset, int image_current, float* xg,
-                                      int* yg) {
-  if (!handle || steps <= 0 || step_offset < 0 || !wprep || !idx_stage || (!xg) != (!yg)) return ecg::kBadArg;
-  int st = check_step_args(L, nc, B, slab_stride, 0, false);
-  if (st) return st;
-  return capture_round(handle, steps, 0, X, L, ldx, idx_stage, Y, params, mom, nc, slab, slab_stride, B, loss_acc, lr,
-                       momentum, wd, nesterov, idx_stage, static_cast<unsigned char*>(wprep), step_offset, image_current,
-                       xg, yg);
-}
-
-// Floats of the gather buffer ``xg`` of ecg_round_graph_create_pf (its ``yg`` holds 2 * B int32).
+// Floats of the gather buffer ``xg`` of a round (its ``yg`` holds 2 * B int32).
 ECG_API long ecg_tiny_gather_floats(int L, int B) { return 2L * B * ((L + 3) / 4 * 4); }
 
 ECG_API int ecg_round_graph_launch(void* handle, hipStream_t stream) {

@@ -203,7 +203,7 @@ def test_prefrag_grads_bitwise_equal_lds_path(B):
 
 @pytest.mark.parametrize("graph", [True, False])
 def test_prefrag_round_graph_bitwise_equal_lds_eager_with_external_updates(graph):
-    """PF round graphs (image rebuilt by the graph's first node, kept by every step's SGD epilogue) reproduce the
+    """PF rounds (image rewritten by the first step's SGD epilogue, kept by every later step's) reproduce the
     LDS-built eager steps bit for bit over several rounds - also after the weights are rewritten between rounds
     (what a FedAvg all-reduce / broadcast does)."""
     from crossscale_ecg.ops.fused_tiny import FusedTinyTrainer
@@ -238,13 +238,10 @@ def test_gather_round_graph_bitwise_equal_plain(L, B):
     from crossscale_ecg.ops.fused_tiny import FusedTinyTrainer
     plan = [7, 1, 2, 3, 7, 4]
     outs = []
-    for gather, graph in ((True, True), (False, True), (False, False)):
+    for gather, graph in ((True, True), (True, False), (False, True), (False, False)):
         dev, x, y, model, _ = _setup(B=B, L=L, N=1024, nc=5)
-        tr = FusedTinyTrainer(model, x, y, B, 7, seed=21, prefrag=True, use_graph=graph)
-        tr.gather = gather
-        if gather and tr.xg is None:
-            tr.xg = torch.zeros(2 * B * ((L + 3) // 4 * 4), dtype=torch.float32, device=dev)
-            tr.yg = torch.zeros(2 * B, dtype=torch.int32, device=dev)
+        tr = FusedTinyTrainer(model, x, y, B, 7, seed=21, prefrag=True, gather=gather, use_graph=graph)
+        assert tr.gather == gather and (tr.xg is not None) == gather
         tr.prepare(sorted(set(plan)))
         for i, n in enumerate(plan):
             tr.run_round(n, reset_loss=False, next_n=plan[i + 1] if i + 1 < len(plan) else None)
@@ -259,3 +256,68 @@ def test_gather_round_graph_bitwise_equal_plain(L, B):
     for o in outs[1:]:
         assert torch.equal(outs[0][0], o[0]) and torch.equal(outs[0][1], o[1])
         assert outs[0][2] == o[2]
+
+
+def _run_plan(tr, plan, staged=False):
+    if staged:
+        tr.prepare(sorted(set(plan)))
+    for i, n in enumerate(plan):
+        tr.run_round(n, reset_loss=False, next_n=plan[i + 1] if staged and i + 1 < len(plan) else None)
+    torch.cuda.synchronize()
+    out = (tr.params.clone(), tr.mom.clone(), tr.avg_loss(), tr.idx_table.clone())
+    tr.close()
+    return out
+
+
+@pytest.mark.parametrize("kw", [dict(precision="fp32"), dict(precision="bf16", prefrag=False)],
+                         ids=["fp32", "bf16-lds"])
+def test_non_pf_rounds_read_staged_table_in_place_bitwise(kw):
+    """Rounds without a PF image follow the same convention as PF rounds - read the staged table in place, then the
+    tables swap: plain graph rounds == prepared graphs with the next round staged behind each round == the eager
+    enqueue, bit for bit."""
+    from crossscale_ecg.ops.fused_tiny import FusedTinyTrainer
+    plan = [5, 5, 3, 5, 2]
+    outs = []
+    for graph, staged in ((True, False), (True, True), (False, False)):
+        dev, x, y, model, _ = _setup(B=64, N=1024)
+        tr = FusedTinyTrainer(model, x, y, 64, 5, seed=21, use_graph=graph, **kw)
+        assert not tr.prefrag and not tr.gather
+        outs.append(_run_plan(tr, plan, staged))
+    for o in outs[1:]:
+        assert torch.equal(outs[0][0], o[0]) and torch.equal(outs[0][1], o[1])
+        assert outs[0][2] == o[2] and torch.equal(outs[0][3][:2], o[3][:2])
+
+
+def test_single_step_without_idx_equals_trainer_step_bitwise():
+    """The Module-1 form of a round (one step, idx = NULL: workgroup b reads row b of the batch buffer) == a
+    one-step trainer round whose table row is 0..B-1."""
+    from crossscale_ecg.bench.module1 import _Compute
+    from crossscale_ecg.ops.fused_tiny import FusedTinyTrainer
+    B, L = 16, 64
+    dev, x, y, model, _ = _setup(B=B, L=L, N=1024)
+    tr = FusedTinyTrainer(model, x, y, B, 1, lr=1e-2, momentum=0.0, seed=3, prefrag=False, use_graph=False)
+    step = _Compute(dev, "fused", B, L)
+    step.flat.copy_(tr.params)
+    step(x[:B].unsqueeze(1), y[:B])
+    tr.stage(1)
+    tr.idx_stage[0].copy_(torch.arange(B, dtype=torch.int32, device=dev))
+    tr.launch_round(1)
+    torch.cuda.synchronize()
+    assert torch.equal(tr.idx_table[0].cpu(), torch.arange(B, dtype=torch.int32))
+    assert torch.equal(step.flat, tr.params)
+    assert torch.equal(step.loss, tr.loss_acc) and step.loss.item() > 0
+    tr.close()
+
+
+def test_one_and_two_step_gather_rounds_graph_equals_enqueue_bitwise():
+    """Round size 1 (only the LDS-built step, nothing gathered) and 2 (the first gathered step) of a PF trainer
+    with gather, on scalar gather rows shorter than a vector multiple (L = 33): graph replay == eager enqueue."""
+    from crossscale_ecg.ops.fused_tiny import FusedTinyTrainer
+    outs = []
+    for graph in (True, False):
+        dev, x, y, model, _ = _setup(B=16, L=33, N=1024)
+        tr = FusedTinyTrainer(model, x, y, 16, 2, seed=21, use_graph=graph)
+        assert tr.prefrag and tr.gather
+        outs.append(_run_plan(tr, [1, 2, 1]))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    assert outs[0][2] == outs[1][2]
