@@ -37,6 +37,12 @@ class FedAvgConfig:
     ckpt_every: int = 0
     ckpt_dir: str = "checkpoints"
     resume: bool = False
+    # evaluation (off by default): after every eval_every-th round each client evaluates the weights a checkpoint
+    # of that round would hold on its last eval_windows windows, which are held out of training (0: on its
+    # training windows); rank 0 appends the summed record to eval_csv
+    eval_every: int = 0
+    eval_windows: int = 0
+    eval_csv: str = "results/fedavg_eval.csv"
     results_csv: str = "results/fedavg_results.csv"
     jsonl: Optional[str] = None
     model: str = "tiny_ecg"

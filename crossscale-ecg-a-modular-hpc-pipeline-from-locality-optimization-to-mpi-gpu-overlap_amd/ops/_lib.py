@@ -74,6 +74,9 @@ def _bind_kernels(lib: C.CDLL) -> None:
     _sig(lib, "ecg_tiny_forward", [vp, i32, i64, vp, vp, i32, vp, i32, i32, vp, vp])
     _sig(lib, "ecg_tiny_wprep_bytes", [])
     _sig(lib, "ecg_tiny_prep", [vp, vp, vp])
+    _sig(lib, "ecg_tiny_eval", [vp, i32, i64, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp])
+    _sig(lib, "ecg_tiny_eval_scratch_bytes", [i32])
+    _sig(lib, "ecg_tiny_eval_out_bytes", [i32])
     _sig(lib, "ecg_slab_reduce_sgd", [vp, i32, i32, i32, vp, vp, vp, vp, f32, f32, f32, i32, i32, vp, vp])
     native = _sig(lib, "ecg_tiny_round_sizeof", [])()
     if native != C.sizeof(TinyRound):

@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from ..models.tiny_ecg import TinyECG, num_params
 from ..data.dataset import DeviceIndexSampler
+from .tiny_eval import EvalResult, TinyEvaluator, evaluate_torch, tiny_evaluate  # noqa: F401  (evaluation: ops/tiny_eval.py)
 
 
 PRECISION = {"bf16": 0, "fp32": 1}
@@ -176,6 +177,7 @@ class FusedTinyTrainer:
         self.use_graph = (os.environ.get("ECG_TINY_GRAPH", "1") != "0") if use_graph is None else bool(use_graph)
         self._graphs = {}  # (n_steps, table pointer) -> native hipGraphExec handle
         self.steps_done = 0
+        self._evaluator: Optional[TinyEvaluator] = None  # evaluate(): buffers allocated on first use
         lib = _lib.kernels()
         L = self.x.shape[1]
         smem = lib.ecg_tiny_smem_bytes(L, self.prec)
@@ -307,6 +309,24 @@ class FusedTinyTrainer:
                        "ecg_tiny_round_enqueue")
         if next_n is not None:
             self.stage(next_n)
+
+    def evaluate(self, x: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None) -> EvalResult:
+        """Loss / accuracy / confusion matrix of the CURRENT weights, in this trainer's precision, on windows ``x``
+        with labels ``y`` (default: its own training windows).  Enqueued on the current stream behind whatever
+        rounds are in flight; reads the weights only (its own prepared-fragment image, scratch and output record are
+        allocated on first use - a round's ``wprep`` is not touched), so the training state is left as it was.  The
+        returned record's metric tensors are reused by the next ``evaluate``."""
+        if (x is None) != (y is None):
+            raise ValueError("evaluate takes both windows and labels, or neither")
+        if x is None:
+            x, y32 = self.x, self.y32
+        else:
+            y32 = y if y.dtype == torch.int32 else labels_int32(y, self.nc)
+        if self.precision != "bf16":
+            return tiny_evaluate(self.params, x, y32, None, self.nc, self.precision)
+        if self._evaluator is None:
+            self._evaluator = TinyEvaluator(self.device, self.nc)
+        return self._evaluator.run(self.params, x, y32)
 
     def avg_loss(self) -> float:
         """Mean per-step loss since the last reset (synchronises)."""

@@ -18,7 +18,15 @@ MI355X execution (vs the reference's host-staged per-tensor MPI calls and per-st
   * ``--overlap delayed``: the all-reduce runs under the next round's local steps (stale-by-one FedAvg);
   * ResNet1D G1 runs on the native step engine (``train.resnet_trainer``; one hipGraph replay per step);
   * ``--sync none``: pseudo-federated independent clients; ``--sync ddp``: synchronous gradient DP;
-  * ``--drop-prob``: client dropout with sample-weighted averaging; ``--ckpt-every``/``--resume``.
+  * ``--drop-prob``: client dropout with sample-weighted averaging; ``--ckpt-every``/``--resume``;
+  * ``--eval-every R`` / ``--eval-windows H``: after every R-th round each client evaluates the weights a checkpoint
+    of that round would hold (the averaged model; ``--sync none``: its own) on its last H windows, which are held
+    out of training (H = 0: on its training windows) - the fused backend on the HIP evaluation kernel
+    (``trainer.evaluate``), every other backend with ``ops.tiny_eval.evaluate_torch``.  The clients' records are
+    summed with one all-reduce and rank 0 appends a row to ``--eval-csv``.  An evaluated round drains its FedAvg
+    all-reduce first, i.e. gives up that round's ``--overlap tail`` overlap (``delayed``: evaluates avg_r in place
+    and keeps the stale correction pending, as a checkpoint does).  Evaluation is timed on its own (``eval_ms``),
+    outside ``local_train_ms`` / ``comm_ms`` / ``round_wall_ms``; the round rows do not change.
 """
 from __future__ import annotations
 
@@ -42,7 +50,7 @@ from ..parallel.overlap import CommRecord, FedAvgComm, FedAvgRound
 from ..utils import profiling, usable_cpus
 from ..utils.ckpt import (ckpt_path, save_checkpoint, load_checkpoint, latest_checkpoint, rank_state_path,
                           save_rank_state, load_trainer_local_state)
-from ..utils.csvio import RoundStats, append_results, ROUND_COLUMNS
+from ..utils.csvio import RoundStats, append_results, ROUND_COLUMNS, EVAL_COLUMNS
 from ..utils.log import RankLogger
 from .local import TorchLocalTrainer
 
@@ -79,6 +87,47 @@ def load_client_data(cfg: FedAvgConfig, ctx: DistContext):
         raise RuntimeError(f"No ecg_*.bin files found in {cfg.data_root}")
     mine = assign_shards_evenly(paths, ctx.world_size, ctx.rank)
     return load_shards_to_gpu(mine, dev, max_windows=cfg.max_windows, labels=cfg.labels)
+
+
+def split_holdout(cfg: FedAvgConfig, x, y, rank: int = 0):
+    """(x_train, y_train, x_eval, y_eval): the last ``eval_windows`` windows are held out of training (views, no
+    copy); 0 evaluates on the training windows themselves."""
+    h = int(cfg.eval_windows)
+    if h < 0 or cfg.eval_every < 0:
+        raise ValueError("--eval-every and --eval-windows must be >= 0")
+    if h == 0:
+        return x, y, x, y
+    if x.shape[0] - h < cfg.batch_size:
+        raise RuntimeError(f"client {rank}: holding out --eval-windows {h} of {x.shape[0]} windows leaves "
+                           f"{max(0, x.shape[0] - h)} training windows < batch {cfg.batch_size}")
+    n = x.shape[0] - h
+    return x[:n], y[:n], x[n:], y[n:]
+
+
+def evaluate_client(trainer, model, backend: str, x_eval, y_eval, ctx: DistContext) -> torch.Tensor:
+    """This client's evaluation record summed over all clients: a float64 vector {loss_sum, count, correct,
+    conf...} on the host (one all-reduce(SUM); the integer counts are exact below 2^53)."""
+    if backend == "fused":
+        res = trainer.evaluate(x_eval, y_eval)
+    else:
+        from ..ops.tiny_eval import evaluate_torch
+        res = evaluate_torch(model, x_eval, y_eval)
+    vec = res.to_vector()
+    if ctx.distributed:
+        import torch.distributed as dist
+        if ctx.backend != "nccl":
+            vec = vec.cpu()
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+    return vec.cpu()
+
+
+def eval_row(cname: str, world: int, r: int, vec: torch.Tensor, nc: int, eval_ms: float, backend: str,
+             precision: str) -> Dict:
+    from ..ops.tiny_eval import EvalResult, confusion_str
+    res = EvalResult.from_vector(vec, nc)
+    return {"config": cname, "world_size": world, "round_idx": r, "windows": res.count, "loss": res.loss,
+            "accuracy": res.accuracy, "confusion": confusion_str(res.confusion), "eval_ms": eval_ms,
+            "backend": backend, "precision": precision}
 
 
 def _amp(cfg: FedAvgConfig):
@@ -195,6 +244,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
     x, y = load_client_data(cfg, ctx)
     if x.shape[0] < cfg.batch_size:
         raise RuntimeError(f"client {ctx.rank} has {x.shape[0]} windows < batch {cfg.batch_size}")
+    x, y, x_eval, y_eval = split_holdout(cfg, x, y, ctx.rank)
     log.info(f"[fedavg] world={ctx.world_size} backend={ctx.backend} device={dev} windows/client={x.shape[0]} "
              f"L={x.shape[1]} B={cfg.batch_size} rounds={cfg.rounds}x{cfg.local_steps} sync={cfg.sync} "
              f"overlap={cfg.overlap}")
@@ -220,6 +270,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         if hasattr(trainer, "prepare"):  # capture + upload + warm the round graphs outside round 0's timing
             trainer.prepare([cfg.local_steps - 1 if seg_tail else cfg.local_steps])
         recs = []
+        evals = []  # (round, summed record, this rank's eval_ms) per evaluated round
         for r in range(start_round, cfg.rounds):
             t_round0 = time.perf_counter()
             rec = CommRecord()
@@ -264,7 +315,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                     elif not seg_tail:
                         fround.end_round(rec)
             due = bool(cfg.ckpt_every) and (r + 1) % cfg.ckpt_every == 0
-            if due and mode != "delayed":
+            eval_due = cfg.eval_every > 0 and (r + 1) % cfg.eval_every == 0
+            if (due or eval_due) and mode != "delayed":
                 fround.finalize()  # checkpoints hold averaged weights (drains an in-flight tail all-reduce)
             avg_loss = trainer.avg_loss()
             if due:
@@ -275,6 +327,13 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                         save_checkpoint(ckpt_path(cfg.ckpt_dir, r, cname), r, model, mom, cname, asdict(cfg))
                 save_rank_state(cfg.ckpt_dir, r, cname, ctx.rank, trainer, client_weights=own)
             recs.append((r, rec, m_l0, m_l1, inner, avg_loss, (time.perf_counter() - t_round0) * 1e3))
+            if eval_due:  # after the round's wall clock stopped; the stream is idle (avg_loss synchronised)
+                _sync(dev)
+                t_e0 = time.perf_counter()
+                with profiling.range("evaluate"), fround.averaged_in_place():  # the weights a checkpoint would hold
+                    vec = evaluate_client(trainer, model, backend, x_eval, y_eval, ctx)
+                    _sync(dev)
+                evals.append((r, vec, (time.perf_counter() - t_e0) * 1e3))
         fround.finalize()
         _sync(dev)
         rows = []
@@ -290,6 +349,18 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
             log.event("round", **asdict(row))
         if hasattr(trainer, "close"):
             trainer.close()
+        if evals:
+            prec = getattr(trainer, "precision", "fp32")
+            all_ms = comm.gather([ms for _, _, ms in evals], root=0)
+            if ctx.rank == 0:
+                erows = [eval_row(cname, ctx.world_size, r, vec, cfg.num_classes, max(ms[i] for ms in all_ms),
+                                  backend, prec) for i, (r, vec, _) in enumerate(evals)]
+                if cfg.eval_csv:
+                    append_results(erows, cfg.eval_csv, EVAL_COLUMNS)
+                for e in erows:
+                    log.event("eval", **e)
+                    log.info(f"[eval] {cname} round {e['round_idx']}: {e['windows']} windows loss {e['loss']:.4f} "
+                             f"accuracy {e['accuracy']:.4f} confusion {e['confusion']} ({e['eval_ms']:.2f} ms)")
         gathered = comm.gather(rows, root=0)
         if ctx.rank == 0:
             flat_rows = [row for rl in gathered for row in rl]

@@ -52,6 +52,10 @@ BENCH_COLUMNS = [f.name for f in fields(BenchStats)]
 ROUND_COLUMNS_REF = ["config", "world_size", "rank", "round_idx", "batch_size", "local_steps", "local_train_ms",
                      "comm_ms", "samples_per_s", "avg_loss"]
 ROUND_COLUMNS = [f.name for f in fields(RoundStats)]
+# one row per (config, evaluated round) of the FedAvg driver (--eval-every): the clients' records summed;
+# ``confusion`` is the row-major matrix [true][pred] in one field ("3 1;0 4"), ``eval_ms`` the maximum over ranks
+EVAL_COLUMNS = ["config", "world_size", "round_idx", "windows", "loss", "accuracy", "confusion", "eval_ms", "backend",
+                "precision"]
 
 LOCALITY_COLUMNS = ["config", "batch_size", "pin_memory", "contiguous", "non_blocking", "data_ms", "h2d_ms",
                     "compute_ms", "step_ms", "samples_per_s"]

@@ -9,6 +9,8 @@ Launch one process per MI355X (RCCL over xGMI):
 New flags: --kernel-backend {auto,fused,torch} --amp-dtype {bf16,fp16,none} --overlap {none,tail,delayed}
 --sync {fedavg,none,ddp} --no-bcast-every-round --ckpt-every N --resume --drop-prob p
 --synthetic-windows N --labels {zeros,parity} --config-file cfg.yaml
+--eval-every R --eval-windows H --eval-csv path (per-round loss / accuracy / confusion of the averaged model on
+each client's held-out last H windows)
 """
 from __future__ import annotations
 
