@@ -515,15 +515,10 @@ struct TinySample {
       }
       return;
     }
-    bf16x8 Bf[3];
+    // fp32 from here on (the bf16 path returned above)
     float Wf[F32_KSTEPS];
-    if constexpr (F32) {
 #pragma unroll
-      for (int s = 0; s < F32_KSTEPS; ++s) Wf[s] = fragF32[s * 64 + lane];
-    } else {
-#pragma unroll
-      for (int s = 0; s < 3; ++s) Bf[s] = *reinterpret_cast<const bf16x8*>(fragF + (s * 64 + lane) * 8);
-    }
+    for (int s = 0; s < F32_KSTEPS; ++s) Wf[s] = fragF32[s * 64 + lane];
     const float b2r = ps[lay.b2 + c];
     float pool = 0.f, cnt = 0.f;
 #pragma unroll
@@ -534,22 +529,12 @@ struct TinySample {
         for (int half = 0; half < 2; ++half) {
           const int t0 = 32 * pair + 16 * half;
           f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-          if constexpr (F32) {
-            // 16x16x4 f32: lane holds A[t0 + (l&15)][r = 4s + h], r = 16*tap + ci
+          // 16x16x4 f32: lane holds A[t0 + (l&15)][r = 4s + h], r = 16*tap + ci
 #pragma unroll
-            for (int s = 0; s < F32_KSTEPS; ++s) {
-              const int r = 4 * s + h, tap = r >> 4, ci = r & 15;
-              const float a = h1s[(t0 + (lane & 15) + tap - 2 + 2) * C + ci];
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Wf[s], acc, 0, 0, 0);
-            }
-          } else {
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-              const int tap = 2 * s + (h >> 1);
-              const int r = t0 + (lane & 15) + tap - 2;  // h1 time index
-              const bf16x8 A = *reinterpret_cast<const bf16x8*>(h1s + (r + 2) * C + 8 * (h & 1));
-              acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, Bf[s], acc, 0, 0, 0);
-            }
+          for (int s = 0; s < F32_KSTEPS; ++s) {
+            const int r = 4 * s + h, tap = r >> 4, ci = r & 15;
+            const float a = h1s[(t0 + (lane & 15) + tap - 2 + 2) * C + ci];
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Wf[s], acc, 0, 0, 0);
           }
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -715,16 +700,15 @@ struct TinySample {
 
   // ---- phase 4: conv2 dgrad (MFMA, A = mask, B = g-scaled w2) * relu'(h1), conv1 wgrad
   __device__ __forceinline__ void dgrad() {
-    // B[r][ci] = g[co] * w2[co][ci][k], r = 32s + 8h + j -> k = r>>4, co = r&15 = 8(h&1) + j
-    float gq[8];
-#pragma unroll
-    for (int q2 = 0; q2 < 2; ++q2) {
-      const float4 v = reinterpret_cast<const float4*>(red + RED_G + 8 * (h & 1))[q2];
-      gq[4 * q2] = v.x; gq[4 * q2 + 1] = v.y; gq[4 * q2 + 2] = v.z; gq[4 * q2 + 3] = v.w;
-    }
-    bf16x8 Bd[3];
-    float Wd[F32_KSTEPS];
     if constexpr (!F32) {
+      // B[r][ci] = g[co] * w2[co][ci][k], r = 32s + 8h + j -> k = r>>4, co = r&15 = 8(h&1) + j
+      float gq[8];
+#pragma unroll
+      for (int q2 = 0; q2 < 2; ++q2) {
+        const float4 v = reinterpret_cast<const float4*>(red + RED_G + 8 * (h & 1))[q2];
+        gq[4 * q2] = v.x; gq[4 * q2 + 1] = v.y; gq[4 * q2 + 2] = v.z; gq[4 * q2 + 3] = v.w;
+      }
+      bf16x8 Bd[3];
       // (g W2) fragments, used as A[ci][(k,co)]
       if constexpr (PF) {
         // The scaled fragments are the same in every wave: the head wave built them into the LDS fragD slots in
@@ -808,18 +792,10 @@ struct TinySample {
       }
       return;
     }
-    if constexpr (F32) {
-      // 16x16x4 f32: B[r][ci], r = 4s + h = 16k + co
+    // fp32 from here on (the bf16 path returned above).  16x16x4 f32: B[r][ci], r = 4s + h = 16k + co
+    float Wd[F32_KSTEPS];
 #pragma unroll
-      for (int s = 0; s < F32_KSTEPS; ++s) Wd[s] = fragD32[s * 64 + lane] * red[RED_G + ((4 * s + h) & 15)];
-    } else {
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        const bf16x8 raw = *reinterpret_cast<const bf16x8*>(fragD + (s * 64 + lane) * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) Bd[s][j] = ecg::to_bf16(ecg::from_bf16(raw[j]) * gq[j]);
-      }
-    }
+    for (int s = 0; s < F32_KSTEPS; ++s) Wd[s] = fragD32[s * 64 + lane] * red[RED_G + ((4 * s + h) & 15)];
     float dw1[K1 + 1];
 #pragma unroll
     for (int k = 0; k <= K1; ++k) dw1[k] = 0.f;
@@ -831,21 +807,11 @@ struct TinySample {
         for (int half = 0; half < 2; ++half) {
           const int t0 = 32 * pair + 16 * half;
           f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-          if constexpr (F32) {
 #pragma unroll
-            for (int s = 0; s < F32_KSTEPS; ++s) {
-              const int r = 4 * s + h, k = r >> 4, co = r & 15;
-              const float a = ms[(t0 + (lane & 15) - k + 2 + 4) * C + co];
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Wd[s], acc, 0, 0, 0);
-            }
-          } else {
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-              const int k = 2 * s + (h >> 1);
-              const int r = t0 + (lane & 15) - k + 2;  // mask time index
-              const bf16x8 A = *reinterpret_cast<const bf16x8*>(ms + (r + 4) * C + 8 * (h & 1));
-              acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, Bd[s], acc, 0, 0, 0);
-            }
+          for (int s = 0; s < F32_KSTEPS; ++s) {
+            const int r = 4 * s + h, k = r >> 4, co = r & 15;
+            const float a = ms[(t0 + (lane & 15) - k + 2 + 4) * C + co];
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Wd[s], acc, 0, 0, 0);
           }
           const int tb = t0 + 4 * h;
           float xw[12];
