@@ -43,6 +43,13 @@ class FedAvgConfig:
     eval_every: int = 0
     eval_windows: int = 0
     eval_csv: str = "results/fedavg_eval.csv"
+    # DP-SGD (off by default; TinyECG on the fused or torch backend): per-sample l2 clip norm C, noise multiplier
+    # sigma (noise std = sigma * C on the summed clipped gradients) and the delta of the reported epsilon; with
+    # dp_clip > 0 rank 0 appends every client's cumulative epsilon per round to privacy_csv
+    dp_clip: float = 0.0
+    dp_noise: float = 0.0
+    dp_delta: float = 1e-5
+    privacy_csv: str = "results/fedavg_privacy.csv"
     results_csv: str = "results/fedavg_results.csv"
     jsonl: Optional[str] = None
     model: str = "tiny_ecg"

@@ -23,6 +23,7 @@ _lock = threading.Lock()
 _libs = {}
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_long, C.c_float
+u64 = C.c_uint64
 f64p = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int)
 i64p = C.POINTER(C.c_int64)
@@ -64,7 +65,8 @@ class TinyRound(C.Structure):
     _fields_ = [("X", vp), ("ldx", i64), ("idx", vp), ("Y", vp), ("params", vp), ("mom", vp), ("slab", vp),
                 ("loss_acc", vp), ("wprep", vp), ("xg", vp), ("yg", vp),
                 ("L", i32), ("nc", i32), ("slab_stride", i32), ("B", i32), ("steps", i32),
-                ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32)]
+                ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32),
+                ("dp_clip", f32), ("dp_sigma", f32), ("dp_seed", u64), ("dp_scale", vp), ("dp_step", vp)]
 
 
 def _bind_kernels(lib: C.CDLL) -> None:
@@ -78,6 +80,9 @@ def _bind_kernels(lib: C.CDLL) -> None:
     _sig(lib, "ecg_tiny_eval_scratch_bytes", [i32])
     _sig(lib, "ecg_tiny_eval_out_bytes", [i32])
     _sig(lib, "ecg_slab_reduce_sgd", [vp, i32, i32, i32, vp, vp, vp, vp, f32, f32, f32, i32, i32, vp, vp])
+    _sig(lib, "ecg_slab_reduce_dp_sgd", [vp, i32, i32, i32, vp, vp, vp, vp, f32, f32, f32, i32, i32, vp,
+                                         f32, f32, u64, vp, vp, vp])
+    _sig(lib, "ecg_dp_noise", [vp, i32, u64, u64, vp])
     native = _sig(lib, "ecg_tiny_round_sizeof", [])()
     if native != C.sizeof(TinyRound):
         raise NativeError(f"EcgTinyRound is {native} bytes in libecg_kernels.so but {C.sizeof(TinyRound)} in "

@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from ..models.tiny_ecg import TinyECG, num_params
 from ..data.dataset import DeviceIndexSampler
+from ..utils.philox import mix64
 from .tiny_eval import EvalResult, TinyEvaluator, evaluate_torch, tiny_evaluate  # noqa: F401  (evaluation: ops/tiny_eval.py)
 
 
@@ -116,6 +117,39 @@ def tiny_step_grads(flat_params: torch.Tensor, x: torch.Tensor, y32: torch.Tenso
     return slab
 
 
+def check_dp_args(dp_clip: float, dp_noise: float) -> None:
+    if not dp_clip >= 0.0 or not dp_noise >= 0.0:
+        raise ValueError(f"dp_clip and dp_noise must be >= 0, got {dp_clip} and {dp_noise}")
+    if dp_noise > 0.0 and dp_clip == 0.0:
+        raise ValueError("dp_noise > 0 needs a clip norm (dp_clip > 0): the noise is scaled by it")
+
+
+def dp_reduce_slab(slab: torch.Tensor, dp_clip: float, dp_noise: float, dp_seed: int, dp_step: torch.Tensor,
+                   num_classes: int = 2):
+    """DP-SGD sum of a gradient slab without an update: returns (grad [P], loss_sum [1], clip factors [B]) where
+    ``grad = sum_b c_b * slab[b] + dp_noise * dp_clip / B * z(dp_seed, t)``, ``t`` the value of ``dp_step`` (int64
+    device word) before the call; the call advances it by one.  The loss column is neither clipped nor noised."""
+    P = num_params(num_classes)
+    grad = torch.empty(P, dtype=torch.float32, device=slab.device)
+    loss = torch.zeros(1, dtype=torch.float32, device=slab.device)
+    scale = torch.empty(slab.shape[0], dtype=torch.float32, device=slab.device)
+    st = _lib.kernels().ecg_slab_reduce_dp_sgd(
+        slab.data_ptr(), slab.shape[0], slab.stride(0), P, None, None, grad.data_ptr(), loss.data_ptr(), 0.0, 0.0, 0.0,
+        0, 0, None, dp_clip, dp_noise, int(dp_seed) & (2 ** 64 - 1), scale.data_ptr(), dp_step.data_ptr(),
+        _lib.stream_ptr(slab.device))
+    _lib.check(st, "ecg_slab_reduce_dp_sgd")
+    return grad, loss, scale
+
+
+def dp_noise(P: int, seed: int, t: int, device) -> torch.Tensor:
+    """Diagnostic: the standard normals z [P] the DP reduce draws for (seed, step t)."""
+    z = torch.empty(P, dtype=torch.float32, device=device)
+    st = _lib.kernels().ecg_dp_noise(z.data_ptr(), P, int(seed) & (2 ** 64 - 1), int(t) & (2 ** 64 - 1),
+                                     _lib.stream_ptr(z.device))
+    _lib.check(st, "ecg_dp_noise")
+    return z
+
+
 def reduce_slab(slab: torch.Tensor, num_classes: int = 2):
     """Sum a gradient slab: returns (grad [P], loss_sum [1]) without applying an update."""
     P = num_params(num_classes)
@@ -141,12 +175,20 @@ class FusedTinyTrainer:
     step kernel reads row b without the dependent idx -> window load (csrc/kernels/tiny_ecg_step.hip GatherArgs).
     Measured: step kernel 7.76 -> 7.52 us and step period 12.35 -> 12.08 us under the kernel tracer (medians of
     687 steps), bench K=500 11.17 -> 11.06 us/step (profiles/r3/tiny_gather_ab.txt).
+
+    DP-SGD (``dp_clip`` > 0): every step clips each sample's gradient to l2 norm ``dp_clip`` and adds Gaussian noise
+    of standard deviation ``dp_noise * dp_clip`` to their sum before the 1/B mean - two launches on the reduce side
+    (clip factors, then the clipped and noised reduce + SGD), the step kernel unchanged.  The noise is Philox
+    (``utils/philox.py``) keyed by ``dp_seed`` (default: a mix of ``seed``) and a 64-bit step counter kept on the
+    device (``dp_step``; host mirror ``dp_steps``), so graph replays, enqueued rounds and the torch backend draw the
+    same values.  The training loss is summed unclipped and un-noised: it is not private.
     """
 
     def __init__(self, model: TinyECG, x_gpu: torch.Tensor, y_gpu: torch.Tensor, batch_size: int,
                  steps_per_round: int, lr: float = 1e-2, momentum: float = 0.9, weight_decay: float = 0.0,
                  nesterov: bool = False, seed: Optional[int] = None, use_graph: Optional[bool] = None,
-                 precision: str = "bf16", prefrag: bool = True, gather: bool = True):
+                 precision: str = "bf16", prefrag: bool = True, gather: bool = True,
+                 dp_clip: float = 0.0, dp_noise: float = 0.0, dp_seed: Optional[int] = None):
         self.device = x_gpu.device
         self.precision = precision
         self.prec = prec_id(precision)
@@ -190,13 +232,23 @@ class FusedTinyTrainer:
         if self.gather:
             self.xg = torch.zeros(lib.ecg_tiny_gather_floats(L, self.B), dtype=torch.float32, device=self.device)
             self.yg = torch.zeros(2 * self.B, dtype=torch.int32, device=self.device)
+        check_dp_args(dp_clip, dp_noise)
+        self.dp_clip, self.dp_noise = float(dp_clip), float(dp_noise)
+        self.dp = self.dp_clip > 0.0
+        self.dp_seed = (mix64(0 if seed is None else seed) if dp_seed is None else int(dp_seed)) & (2 ** 64 - 1)
+        self.dp_steps = 0  # host mirror of dp_step, counted like steps_done
+        self.dp_scale = self.dp_step = None
+        if self.dp:
+            self.dp_scale = torch.zeros(self.B, dtype=torch.float32, device=self.device)
+            self.dp_step = torch.zeros(1, dtype=torch.int64, device=self.device)
         # the native description of a round; ``idx`` and ``steps`` are set per round (_round_of)
         self._round = _lib.TinyRound(
             X=self.x.data_ptr(), ldx=self.x.stride(0), Y=self.y32.data_ptr(), params=self.params.data_ptr(),
             mom=self.mom.data_ptr(), slab=self.slab.data_ptr(), loss_acc=self.loss_acc.data_ptr(),
             wprep=_lib.ptr(self.wprep), xg=_lib.ptr(self.xg), yg=_lib.ptr(self.yg), L=L, nc=self.nc,
             slab_stride=self.stride, B=self.B, lr=self.lr, momentum=self.momentum, wd=self.wd,
-            nesterov=int(self.nesterov), prec=self.prec)
+            nesterov=int(self.nesterov), prec=self.prec, dp_clip=self.dp_clip, dp_sigma=self.dp_noise,
+            dp_seed=self.dp_seed, dp_scale=_lib.ptr(self.dp_scale), dp_step=_lib.ptr(self.dp_step))
 
     # ------------------------------------------------------------------ graph management
     def _round_of(self, n: int, table: torch.Tensor):
@@ -232,14 +284,16 @@ class FusedTinyTrainer:
     def prepare(self, sizes) -> None:
         """Draw the sampler's first permutation block, then capture, upload and warm every round graph whose step
         count is in ``sizes`` (on both index buffers), so a later round of that size only replays.  The warm-up
-        replay is rolled back (weights, momentum, loss, staged batches are restored): it leaves the training state
-        exactly as it found it."""
+        replay is rolled back (weights, momentum, loss, staged batches and the DP step counter are restored): it
+        leaves the training state exactly as it found it."""
         self.sampler.prime()
         if not self.use_graph:
             return
         lib = _lib.kernels()
         sizes = [self._check_n(n) for n in sizes]
         state = (self.params, self.mom, self.loss_acc, self.idx_stage, self.idx_table)
+        if self.dp:
+            state += (self.dp_step,)
         snap = [t.clone() for t in state]
         stream = _lib.stream_ptr(self.device)
         for n in sizes:
@@ -287,6 +341,8 @@ class FusedTinyTrainer:
         self.idx_table, self.idx_stage = self.idx_stage, self.idx_table
         self.steps_done += n
         self._loss_steps += n
+        if self.dp:
+            self.dp_steps += n
         return self.idx_table
 
     def run_round(self, n_steps: Optional[int] = None, reset_loss: bool = True, next_n: Optional[int] = None) -> None:
@@ -334,3 +390,9 @@ class FusedTinyTrainer:
 
     def reset_momentum(self):
         self.mom.zero_()
+
+    def set_dp_steps(self, n: int) -> None:
+        """Continue the noise stream at step ``n`` (checkpoint resume)."""
+        self.dp_steps = int(n)
+        if self.dp:
+            self.dp_step.fill_(int(n))

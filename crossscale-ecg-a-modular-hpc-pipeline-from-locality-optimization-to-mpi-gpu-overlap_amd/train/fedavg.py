@@ -27,6 +27,12 @@ MI355X execution (vs the reference's host-staged per-tensor MPI calls and per-st
     all-reduce first, i.e. gives up that round's ``--overlap tail`` overlap (``delayed``: evaluates avg_r in place
     and keeps the stale correction pending, as a checkpoint does).  Evaluation is timed on its own (``eval_ms``),
     outside ``local_train_ms`` / ``comm_ms`` / ``round_wall_ms``; the round rows do not change.
+  * ``--dp-clip C`` / ``--dp-noise sigma`` / ``--dp-delta delta``: DP-SGD local steps (per-sample clip to l2 norm C,
+    Gaussian noise sigma * C on the clipped sum) for TinyECG on the fused and torch backends; every client's DP seed
+    is a 64-bit mix of ``seed + 7919 * rank``.  Each round every client logs its cumulative epsilon
+    (``utils.privacy``: the Poisson-subsampling bound at ``sample_rate = batch / training windows``, an approximation
+    for the epoch-permutation sampler used here) and rank 0 appends the rows to ``--privacy-csv``.  The training loss in
+    the round rows is computed from unclipped, un-noised per-sample losses: it is not private.
 """
 from __future__ import annotations
 
@@ -50,7 +56,9 @@ from ..parallel.overlap import CommRecord, FedAvgComm, FedAvgRound
 from ..utils import profiling, usable_cpus
 from ..utils.ckpt import (ckpt_path, save_checkpoint, load_checkpoint, latest_checkpoint, rank_state_path,
                           save_rank_state, load_trainer_local_state)
-from ..utils.csvio import RoundStats, append_results, ROUND_COLUMNS, EVAL_COLUMNS
+from ..utils.csvio import RoundStats, append_results, ROUND_COLUMNS, EVAL_COLUMNS, PRIVACY_COLUMNS
+from ..utils.philox import mix64
+from ..utils.privacy import epsilon as dp_epsilon
 from ..utils.log import RankLogger
 from .local import TorchLocalTrainer
 
@@ -134,13 +142,37 @@ def _amp(cfg: FedAvgConfig):
     return {"bf16": torch.bfloat16, "fp16": torch.float16, "none": None}[cfg.amp_dtype]
 
 
+def check_dp_config(cfg: FedAvgConfig, config_name: str, backend: str) -> None:
+    """DP-SGD exists for TinyECG on the fused and torch backends, in fp32 or bf16, with local rounds."""
+    if cfg.dp_clip < 0 or cfg.dp_noise < 0:
+        raise ValueError("--dp-clip and --dp-noise must be >= 0")
+    if cfg.dp_noise > 0 and cfg.dp_clip == 0:
+        raise ValueError("--dp-noise needs --dp-clip > 0: the noise is scaled by the clip norm")
+    if cfg.dp_clip == 0:
+        return
+    if not 0.0 < cfg.dp_delta < 1.0:
+        raise ValueError("--dp-delta must be in (0, 1)")
+    if backend == "hip" or cfg.model != "tiny_ecg":
+        raise ValueError("DP-SGD (--dp-clip) is implemented for TinyECG on the fused and torch backends, not for "
+                         "the ResNet1D engine (--kernel-backend hip)")
+    if config_name == "G1" and cfg.amp_dtype == "fp16":
+        raise ValueError("DP-SGD (--dp-clip) does not support fp16 AMP: its GradScaler would rescale the clipped "
+                         "gradients; use --amp-dtype bf16 or none")
+    if cfg.sync == "ddp":
+        raise ValueError("DP-SGD (--dp-clip) does not support --sync ddp: " + (
+            "the fused backend's per-step gradient all-reduce bypasses the round that clips and adds noise"
+            if backend == "fused" else "per-sample gradients bypass DistributedDataParallel's gradient hooks"))
+
+
 def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistContext, backend: str):
     seed = cfg.seed + 7919 * ctx.rank
+    check_dp_config(cfg, config_name, backend)
+    dp = dict(dp_clip=cfg.dp_clip, dp_noise=cfg.dp_noise, dp_seed=mix64(seed))
     if backend == "fused":
         from ..ops.fused_tiny import FusedTinyTrainer
         prec = "bf16" if (config_name == "G1" and cfg.amp_dtype == "bf16") else "fp32"
         return FusedTinyTrainer(model, x, y, cfg.batch_size, cfg.local_steps, lr=cfg.lr, momentum=cfg.momentum,
-                                seed=seed, precision=prec)
+                                seed=seed, precision=prec, **dp)
     if backend == "hip":  # ResNet1D on the native step engine
         from .resnet_trainer import ResNetEngineTrainer
         return ResNetEngineTrainer(model, x, y, cfg.batch_size, cfg.local_steps, lr=cfg.lr, momentum=cfg.momentum,
@@ -150,7 +182,8 @@ def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistCont
     if cfg.sync == "ddp" and ctx.distributed:
         from torch.nn.parallel import DistributedDataParallel as DDP
         net = DDP(model, device_ids=[dev_index(ctx)] if ctx.device.type == "cuda" else None, bucket_cap_mb=cfg.bucket_mb)
-    return TorchLocalTrainer(net, x, y, cfg.batch_size, lr=cfg.lr, momentum=cfg.momentum, amp_dtype=amp, seed=seed)
+    return TorchLocalTrainer(net, x, y, cfg.batch_size, lr=cfg.lr, momentum=cfg.momentum, amp_dtype=amp, seed=seed,
+                             **dp)
 
 
 def dev_index(ctx):
@@ -249,6 +282,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
              f"L={x.shape[1]} B={cfg.batch_size} rounds={cfg.rounds}x{cfg.local_steps} sync={cfg.sync} "
              f"overlap={cfg.overlap}")
     configs = ["G0", "G1"] if cfg.config == "both" else [cfg.config]
+    for cname in configs:  # an unsupported DP-SGD combination stops the run before any configuration trains
+        check_dp_config(cfg, cname, pick_backend(cfg, cname, ctx))
     all_rows: List[Dict] = []
     fcomm = FedAvgComm(ctx)
     for cname in configs:
@@ -271,6 +306,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
             trainer.prepare([cfg.local_steps - 1 if seg_tail else cfg.local_steps])
         recs = []
         evals = []  # (round, summed record, this rank's eval_ms) per evaluated round
+        privacy = []  # DP-SGD: this client's cumulative (round, steps, epsilon)
+        sample_rate = cfg.batch_size / x.shape[0]
         for r in range(start_round, cfg.rounds):
             t_round0 = time.perf_counter()
             rec = CommRecord()
@@ -302,6 +339,9 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                 if seg_tail:  # the round's last step, its segment all-reduces overlapping its own backward
                     trainer.tail_fedavg(fcomm, rec)
             m_l1 = fcomm.mark()
+            if cfg.dp_clip > 0:
+                privacy.append((r, trainer.dp_steps,
+                                dp_epsilon(cfg.dp_noise, sample_rate, trainer.dp_steps, cfg.dp_delta)))
             # the stall on the previous round's collective happened inside [m_l0, m_l1]: not local work
             inner = prev_rec.stalls[stalls0:] if prev_rec is not None else []
             inner = inner + (rec.stalls if seg_tail else [])
@@ -361,6 +401,23 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                     log.event("eval", **e)
                     log.info(f"[eval] {cname} round {e['round_idx']}: {e['windows']} windows loss {e['loss']:.4f} "
                              f"accuracy {e['accuracy']:.4f} confusion {e['confusion']} ({e['eval_ms']:.2f} ms)")
+        if privacy:
+            prows = [{"config": cname, "world_size": ctx.world_size, "rank": ctx.rank, "round_idx": r, "steps": steps,
+                      "sample_rate": sample_rate, "noise_multiplier": cfg.dp_noise, "clip_norm": cfg.dp_clip,
+                      "delta": cfg.dp_delta, "epsilon": eps} for r, steps, eps in privacy]
+            for row in prows:
+                log.event("privacy", **row)
+            all_prows = comm.gather(prows, root=0)
+            if ctx.rank == 0:
+                # one row per round: the client with the largest epsilon (clients differ when their shards do)
+                worst = [max(per_round, key=lambda d: d["epsilon"]) for per_round in zip(*all_prows)]
+                if cfg.privacy_csv:
+                    append_results(worst, cfg.privacy_csv, PRIVACY_COLUMNS)
+                last = worst[-1]
+                log.info(f"[privacy] {cname}: after round {last['round_idx']} ({last['steps']} steps, q="
+                         f"{last['sample_rate']:.4g}, sigma={cfg.dp_noise:g}, C={cfg.dp_clip:g}) epsilon <= "
+                         f"{last['epsilon']:.4g} at delta={cfg.dp_delta:g} (Poisson-sampling bound; the training "
+                         "loss is not private)")
         gathered = comm.gather(rows, root=0)
         if ctx.rank == 0:
             flat_rows = [row for rl in gathered for row in rl]

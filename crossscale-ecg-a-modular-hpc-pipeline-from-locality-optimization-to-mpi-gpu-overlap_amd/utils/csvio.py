@@ -56,6 +56,10 @@ ROUND_COLUMNS = [f.name for f in fields(RoundStats)]
 # ``confusion`` is the row-major matrix [true][pred] in one field ("3 1;0 4"), ``eval_ms`` the maximum over ranks
 EVAL_COLUMNS = ["config", "world_size", "round_idx", "windows", "loss", "accuracy", "confusion", "eval_ms", "backend",
                 "precision"]
+# one row per (config, round) of a DP-SGD run (--dp-clip): the cumulative epsilon after that round of the client
+# with the largest one (utils/privacy.py: the Poisson-subsampling RDP bound at sample_rate = batch / training windows)
+PRIVACY_COLUMNS = ["config", "world_size", "round_idx", "steps", "sample_rate", "noise_multiplier", "clip_norm",
+                   "delta", "epsilon"]
 
 LOCALITY_COLUMNS = ["config", "batch_size", "pin_memory", "contiguous", "non_blocking", "data_ms", "h2d_ms",
                     "compute_ms", "step_ms", "samples_per_s"]

@@ -1104,6 +1104,165 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_sgd_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------- DP-SGD (per-sample clip + noise)
+// The slab already holds one gradient row per sample, so DP-SGD only changes the reduce side: a row-norm launch
+// writes the clip factors c_b = min(1, C / n_b) and ``slab_reduce_sgd_kernel``'s twin sums c_b * row_b, adds
+// sigma * C / B * z_i and runs the same SGD / wprep / gather epilogue.  The step kernel is not involved.
+//
+// Noise is counter-based so that a graph replay, an enqueued round and the torch backend (utils/philox.py) draw the
+// same z: Philox4x32-10 (Salmon et al., SC'11) with counter (i, t lo, t hi, 0) and key (seed lo, seed hi), i the
+// parameter index and t the 64-bit DP step counter; u1 = ((w0 >> 8) + 1) * 2^-24 in (0, 1], u2 = (w1 >> 8) * 2^-24
+// in [0, 1), z = sqrt(-2 ln u1) * cos(2 pi u2) with the accurate logf / sqrtf / cosf (|z| <= 5.77).
+__host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    c[1] = (uint32_t)p1;
+    c[3] = (uint32_t)p0;
+    c[0] = n0;
+    c[2] = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+__device__ inline float dp_normal(int i, unsigned long long seed, unsigned long long t) {
+  uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)(t >> 32), 0u};
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const float u1 = (float)((c[0] >> 8) + 1u) * 0x1p-24f, u2 = (float)(c[1] >> 8) * 0x1p-24f;
+  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+}
+
+// Diagnostic: z[i] for i < P of step t (the values the DP reduce adds, without the sigma * C / B factor).
+// (The DP kernels are templates so that hipcc emits them after every older kernel of this file: the older kernels'
+// assembly, label numbers included, stays what scripts/diff_device_asm.py saw before DP-SGD existed.)
+template <int NT>
+__global__ __launch_bounds__(NT) void dp_noise_kernel(float* __restrict__ z, int P, unsigned long long seed,
+                                                      unsigned long long t) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i < P) z[i] = dp_normal(i, seed, t);
+}
+
+// Clip factors of one step's slab: one wave per row, scale[b] = min(1, clip / n_b) with n_b = B * |row_b[0:P]|_2 (the
+// step kernel stores rows pre-scaled by 1/B; the loss column P is not part of the norm; n_b == 0 -> 1).  Fixed
+// summation order (per lane in column order, then a butterfly over the wave), no atomics.  vec: 16-byte loads
+// (rows 16-byte aligned, stride % 4 == 0 so the last row's padding is readable).  Thread 0 of block 0 advances the DP
+// step counter: it is the counter's only writer, and its only reader is the DP reduce launched next, which
+// therefore draws step ``dp_step[0] - 1``.  Kernel arguments are baked into a captured graph; a device word is not.
+constexpr int DP_ROWS_PER_BLOCK = 4;
+template <int ROWS>
+__global__ __launch_bounds__(ROWS * 64) void dp_row_scale_kernel(
+    const float* __restrict__ slab, int G, int stride, int P, float clip, float* __restrict__ scale,
+    unsigned long long* __restrict__ dp_step, int vec) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) dp_step[0] = dp_step[0] + 1ull;
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * ROWS + (threadIdx.x >> 6);
+  if (b >= G) return;  // wave-uniform
+  const float* row = slab + (long)b * stride;
+  float ss = 0.f;
+  if (vec) {
+    for (int c0 = 4 * lane; c0 < P; c0 += 256) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(row + c0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ss += (c0 + j < P) ? v[j] * v[j] : 0.f;
+    }
+  } else {
+    for (int c0 = lane; c0 < P; c0 += 64) {
+      const float v = row[c0];
+      ss += v * v;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  if (lane == 0) {
+    const float n = (float)G * sqrtf(ss);
+    scale[b] = n > 0.f ? fminf(1.f, clip / n) : 1.f;
+  }
+}
+
+// ``slab_reduce_sgd_kernel`` with every loaded gradient value multiplied by its row's clip factor and
+// ``noise_scale`` * z_col added to the column sum before the epilogue (noise_scale = sigma * C / B; 0: no noise is
+// drawn).  Same column-to-block map, row chunking and summation order: with every scale[b] == 1 and noise_scale == 0
+// the results are bitwise the plain kernel's.  The loss column is neither scaled nor noised.
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_dp_sgd_kernel(
+    const float* __restrict__ slab, int G, int stride, int P,
+    float* __restrict__ params, float* __restrict__ mom, float* __restrict__ grad_out,
+    float* __restrict__ loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
+    unsigned char* __restrict__ wprep, const float* __restrict__ scale, float noise_scale, unsigned long long seed,
+    const unsigned long long* __restrict__ dp_step, GatherArgs ga) {
+  constexpr int NT = RED_COLS * RED_ROWG;
+  if ((int)blockIdx.x >= ga.nred) {  // block-uniform: gather blocks never reach the barrier below
+    const int per_row = ga.vec ? ga.L / 4 : ga.L;
+    const int rpb = gather_rows_per_block(ga.L, ga.vec, NT);
+    const int r0 = ((int)blockIdx.x - ga.nred) * rpb;
+    const __amdgpu_buffer_rsrc_t xr = make_rsrc(ga.xg, (long)ga.B * ga.ldg * 4);
+    for (int e = threadIdx.x; e < rpb * per_row; e += NT) {
+      const int lr_ = e / per_row, j = e - lr_ * per_row, b = r0 + lr_;
+      if (b >= ga.B) break;  // e only grows, so every later e is past the batch too
+      const long row = ga.idx[b];
+      if (ga.vec) {
+        st_wt4(xr, b * ga.ldg + 4 * j, *reinterpret_cast<const f32x4*>(ga.X + row * ga.ldx + 4 * j));
+      } else {
+        st_wt(xr, b * ga.ldg + j, ga.X[row * ga.ldx + j]);
+      }
+      if (j == 0) ga.yg[b] = ga.Y[row];
+    }
+    return;
+  }
+  __shared__ float part[RED_ROWG][RED_COLS + 1];
+  const int cl = threadIdx.x % RED_COLS, rg = threadIdx.x / RED_COLS;
+  const int col = blockIdx.x * RED_COLS + cl;
+  const bool upd = rg == 0 && col < P && apply;
+  const float p0 = upd ? params[col] : 0.f;
+  const float m0 = (upd && momentum != 0.f) ? mom[col] : 0.f;
+  float noise = 0.f;  // drawn before the slab reads, under their latency
+  if (rg == 0 && col < P && noise_scale != 0.f) noise = noise_scale * dp_normal(col, seed, dp_step[0] - 1ull);
+  float s = 0.f;
+  if (col <= P) {
+    const float* base = slab + col;
+    const bool grad_col = col < P;  // the loss column is summed as it is
+    int r = rg;
+    for (; r + RED_ROWG * 15 < G; r += RED_ROWG * 16) {
+      float v[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int rr = r + RED_ROWG * j;
+        v[j] = base[(long)rr * stride] * (grad_col ? scale[rr] : 1.f);
+      }
+#pragma unroll
+      for (int j = 0; j < 16; j += 2) s += v[j] + v[j + 1];
+    }
+    for (; r < G; r += RED_ROWG) s += base[(long)r * stride] * (grad_col ? scale[r] : 1.f);
+  }
+  part[rg][cl] = s;
+  __syncthreads();
+  if (rg == 0 && col <= P) {
+    float gsum = 0.f;
+#pragma unroll
+    for (int j = 0; j < RED_ROWG; ++j) gsum += part[j][cl];
+    if (col == P) {
+      if (loss_acc) loss_acc[0] += gsum;
+    } else {
+      if (noise_scale != 0.f) gsum += noise;
+      if (grad_out) grad_out[col] = gsum;
+      if (apply) {
+        const float p = p0;
+        float d = gsum + wd * p;
+        if (momentum != 0.f) {
+          const float bm = momentum * m0 + d;
+          mom[col] = bm;
+          d = nesterov ? d + momentum * bm : bm;
+        }
+        const float pn = p - lr * d;
+        params[col] = pn;
+        if (wprep) wprep_put(wprep, col, pn);
+      }
+    }
+  }
+}
+
 unsigned long long* g_stamps = nullptr;  // diagnostic phase stamps (ecg_tiny_set_stamps)
 
 FusedOpt no_fuse() {
@@ -1222,6 +1381,49 @@ int reduce_dispatch(const float* slab, int G, int stride, int P, float* params, 
   return ecg::kOk;
 }
 
+// DP-SGD settings of a reduce: clip > 0 (sigma >= 0), the [G] clip-factor vector and the device step counter.
+struct DpArgs {
+  float clip, sigma;
+  unsigned long long seed;
+  float* scale;
+  unsigned long long* step;
+};
+int check_dp(const DpArgs& d) {
+  if (d.clip <= 0.f || d.sigma < 0.f || !d.scale || !d.step) return ecg::kBadArg;
+  return ecg::kOk;
+}
+
+// The DP pair of one step: clip factors (and the counter advance), then the clipped, noised reduce + SGD.
+int dp_reduce_dispatch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
+                       float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
+                       unsigned char* wprep, const DpArgs& dp, hipStream_t stream, const GatherArgs* gather = nullptr) {
+  if (G <= 0 || P <= 0 || stride < P + 1 || !slab) return ecg::kBadArg;
+  if (apply && (!params || (momentum != 0.f && !mom))) return ecg::kBadArg;
+  const int st = check_dp(dp);
+  if (st) return st;
+  const int vec = (stride % 4 == 0 && reinterpret_cast<uintptr_t>(slab) % 16 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(dp_row_scale_kernel<DP_ROWS_PER_BLOCK>, dim3((G + DP_ROWS_PER_BLOCK - 1) / DP_ROWS_PER_BLOCK),
+                     dim3(DP_ROWS_PER_BLOCK * 64), 0, stream, slab, G, stride, P, dp.clip, dp.scale, dp.step, vec);
+  ECG_HIP_CHECK(hipGetLastError());
+  constexpr int cols = kRedColsDefault;
+  const int blocks = (P + 1 + cols - 1) / cols;
+  GatherArgs ga{};
+  ga.nred = INT_MAX;
+  int grid = blocks;
+  if (gather) {
+    ga = *gather;
+    ga.nred = blocks;
+    const int rpb = gather_rows_per_block(ga.L, ga.vec, cols * RED_ROWG);
+    grid += (ga.B + rpb - 1) / rpb;
+  }
+  const float noise_scale = dp.sigma * dp.clip / (float)G;
+  hipLaunchKernelGGL(slab_reduce_dp_sgd_kernel<cols>, dim3(grid), dim3(cols * RED_ROWG), 0, stream, slab, G, stride, P,
+                     params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply, wprep, dp.scale, noise_scale,
+                     dp.seed, dp.step, ga);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
 struct RoundGraph {
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
@@ -1304,8 +1506,29 @@ ECG_API int ecg_slab_reduce_sgd(const float* slab, int G, int stride, int P, flo
                          static_cast<unsigned char*>(wprep), stream);
 }
 
-// A local round: ``steps`` times "step kernel, then reduce + SGD kernel".  ops/_lib.py mirrors this struct field
-// for field and compares its size with ecg_tiny_round_sizeof() when it binds the library.
+// DP-SGD twin of ecg_slab_reduce_sgd (two launches): clip factors of the slab's rows into ``dp_scale`` [G] and
+// ``dp_step[0]`` += 1, then the sum of dp_scale[b] * row_b plus dp_sigma * dp_clip / G * z(dp_seed, step, column),
+// where ``step`` is the value ``dp_step[0]`` held before the call, through the same SGD epilogue.
+ECG_API int ecg_slab_reduce_dp_sgd(const float* slab, int G, int stride, int P, float* params, float* mom,
+                                   float* grad_out, float* loss_acc, float lr, float momentum, float wd, int nesterov,
+                                   int apply, void* wprep, float dp_clip, float dp_sigma, unsigned long long dp_seed,
+                                   float* dp_scale, unsigned long long* dp_step, hipStream_t stream) {
+  if (wprep && !apply) return ecg::kBadArg;
+  return dp_reduce_dispatch(slab, G, stride, P, params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply,
+                            static_cast<unsigned char*>(wprep), {dp_clip, dp_sigma, dp_seed, dp_scale, dp_step}, stream);
+}
+
+// Diagnostic: z[0:P], the standard normals the DP reduce draws for (seed, step t).
+ECG_API int ecg_dp_noise(float* z, int P, unsigned long long seed, unsigned long long t, hipStream_t stream) {
+  if (!z || P <= 0) return ecg::kBadArg;
+  hipLaunchKernelGGL(dp_noise_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, z, P, seed, t);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+// A local round: ``steps`` times "step kernel, then reduce + SGD kernel" (DP-SGD: step kernel, clip factors, clipped
+// and noised reduce + SGD).  ops/_lib.py mirrors this struct field for field and compares its size with
+// ecg_tiny_round_sizeof() when it binds the library.
 struct EcgTinyRound {
   const float* X;  // dataset windows [N][ldx], window length L
   long ldx;
@@ -1322,6 +1545,12 @@ struct EcgTinyRound {
   int L, nc, slab_stride, B, steps;
   float lr, momentum, wd;
   int nesterov, prec;
+  // DP-SGD (dp_clip > 0): per-sample clip norm C, noise multiplier sigma, the Philox key, the [B] clip factors
+  // (scratch) and the 64-bit step counter (device word, advanced by every step).  dp_clip == 0: today's launches.
+  float dp_clip, dp_sigma;
+  unsigned long long dp_seed;
+  float* dp_scale;
+  unsigned long long* dp_step;
 };
 
 ECG_API int ecg_tiny_round_sizeof(void) { return (int)sizeof(EcgTinyRound); }
@@ -1331,10 +1560,12 @@ static int check_round(const EcgTinyRound* r) {
   if (r->prec != 0 && r->prec != 1) return ecg::kBadArg;
   if (r->wprep && r->prec != 0) return ecg::kBadArg;
   if ((!r->xg) != (!r->yg) || (r->xg && (!r->wprep || !r->idx))) return ecg::kBadArg;
+  if (r->dp_clip < 0.f || r->dp_sigma < 0.f || (r->dp_sigma > 0.f && r->dp_clip == 0.f)) return ecg::kBadArg;
+  if (r->dp_clip > 0.f && (!r->dp_scale || !r->dp_step)) return ecg::kBadArg;
   return check_step_args(r->L, r->nc, r->B, r->slab_stride, 0, r->prec == 1);
 }
 
-// Enqueue a checked round on ``stream`` (a capturing stream included): two launches per step.
+// Enqueue a checked round on ``stream`` (a capturing stream included): two launches per step, three with DP-SGD.
 // (Warm-up loads of the next step's windows in the step kernel's tail measured neutral - 11.11 vs 11.08 us/step,
 // the windows already sit in the Infinity Cache; profiles/r2/bench_prefetch.txt - and were removed.)
 static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
@@ -1364,8 +1595,13 @@ static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
     }
     int st = step_dispatch(0, r.prec, a, stream);
     if (st) return st;
-    st = reduce_dispatch(r.slab, r.B, r.slab_stride, P, r.params, r.mom, nullptr, r.loss_acc, r.lr, r.momentum, r.wd,
-                         r.nesterov, 1, wprep, stream, gather_next ? &ga : nullptr);
+    if (r.dp_clip > 0.f)
+      st = dp_reduce_dispatch(r.slab, r.B, r.slab_stride, P, r.params, r.mom, nullptr, r.loss_acc, r.lr, r.momentum,
+                              r.wd, r.nesterov, 1, wprep, {r.dp_clip, r.dp_sigma, r.dp_seed, r.dp_scale, r.dp_step},
+                              stream, gather_next ? &ga : nullptr);
+    else
+      st = reduce_dispatch(r.slab, r.B, r.slab_stride, P, r.params, r.mom, nullptr, r.loss_acc, r.lr, r.momentum, r.wd,
+                           r.nesterov, 1, wprep, stream, gather_next ? &ga : nullptr);
     if (st) return st;
   }
   return ecg::kOk;

@@ -11,6 +11,8 @@ New flags: --kernel-backend {auto,fused,torch} --amp-dtype {bf16,fp16,none} --ov
 --synthetic-windows N --labels {zeros,parity} --config-file cfg.yaml
 --eval-every R --eval-windows H --eval-csv path (per-round loss / accuracy / confusion of the averaged model on
 each client's held-out last H windows)
+--dp-clip C --dp-noise sigma --dp-delta delta --privacy-csv path (DP-SGD local steps: per-sample clip + Gaussian
+noise; cumulative epsilon per round, Poisson-subsampling bound; the reported training loss is not private)
 """
 from __future__ import annotations
 
