@@ -66,7 +66,8 @@ class TinyRound(C.Structure):
                 ("loss_acc", vp), ("wprep", vp), ("xg", vp), ("yg", vp),
                 ("L", i32), ("nc", i32), ("slab_stride", i32), ("B", i32), ("steps", i32),
                 ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32),
-                ("dp_clip", f32), ("dp_sigma", f32), ("dp_seed", u64), ("dp_scale", vp), ("dp_step", vp)]
+                ("dp_clip", f32), ("dp_sigma", f32), ("dp_seed", u64), ("dp_scale", vp), ("dp_step", vp),
+                ("xbg", vp)]
 
 
 def _bind_kernels(lib: C.CDLL) -> None:
@@ -90,6 +91,7 @@ def _bind_kernels(lib: C.CDLL) -> None:
     _sig(lib, "ecg_tiny_round_enqueue", [C.POINTER(TinyRound), vp])
     _sig(lib, "ecg_tiny_round_capture", [C.POINTER(vp), C.POINTER(TinyRound)])
     _sig(lib, "ecg_tiny_gather_floats", [i32, i32], i64)
+    _sig(lib, "ecg_tiny_gather_halfs", [i32, i32], i64)
     _sig(lib, "ecg_tiny_step_grads_twice", [vp, i32, i64, vp, vp, vp, i32, vp, i32, i32, f32, i32, vp, vp])
     _sig(lib, "ecg_tiny_force_waves", [i32])
     _sig(lib, "ecg_tiny_set_stamps", [vp])

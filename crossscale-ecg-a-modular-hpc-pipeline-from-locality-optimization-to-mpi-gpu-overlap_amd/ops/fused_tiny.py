@@ -176,6 +176,13 @@ class FusedTinyTrainer:
     Measured: step kernel 7.76 -> 7.52 us and step period 12.35 -> 12.08 us under the kernel tracer (medians of
     687 steps), bench K=500 11.17 -> 11.06 us/step (profiles/r3/tiny_gather_ab.txt).
 
+    ``pack`` (needs ``gather``): the gather also writes every window as a packed bf16 row - zero pads on both sides
+    standing in for the conv padding - into a second ping-pong buffer ``xbg``, and the gathered steps run the step
+    kernel variant that loads its conv1 operand from those rows (one 16-byte load and a one-element shift per time
+    step instead of 7 floats, 7 conversions and the edge handling).  The operand is bitwise the same, so
+    ``pack=False`` - the round exactly as it was, ``xg`` rows into the unpacked kernel - gives identical results.
+    ``xg`` is written either way.
+
     DP-SGD (``dp_clip`` > 0): every step clips each sample's gradient to l2 norm ``dp_clip`` and adds Gaussian noise
     of standard deviation ``dp_noise * dp_clip`` to their sum before the 1/B mean - two launches on the reduce side
     (clip factors, then the clipped and noised reduce + SGD), the step kernel unchanged.  The noise is Philox
@@ -187,7 +194,7 @@ class FusedTinyTrainer:
     def __init__(self, model: TinyECG, x_gpu: torch.Tensor, y_gpu: torch.Tensor, batch_size: int,
                  steps_per_round: int, lr: float = 1e-2, momentum: float = 0.9, weight_decay: float = 0.0,
                  nesterov: bool = False, seed: Optional[int] = None, use_graph: Optional[bool] = None,
-                 precision: str = "bf16", prefrag: bool = True, gather: bool = True,
+                 precision: str = "bf16", prefrag: bool = True, gather: bool = True, pack: bool = True,
                  dp_clip: float = 0.0, dp_noise: float = 0.0, dp_seed: Optional[int] = None):
         self.device = x_gpu.device
         self.precision = precision
@@ -232,6 +239,10 @@ class FusedTinyTrainer:
         if self.gather:
             self.xg = torch.zeros(lib.ecg_tiny_gather_floats(L, self.B), dtype=torch.float32, device=self.device)
             self.yg = torch.zeros(2 * self.B, dtype=torch.int32, device=self.device)
+        self.pack = bool(pack) and self.gather
+        self.xbg = None
+        if self.pack:
+            self.xbg = torch.zeros(lib.ecg_tiny_gather_halfs(L, self.B), dtype=torch.bfloat16, device=self.device)
         check_dp_args(dp_clip, dp_noise)
         self.dp_clip, self.dp_noise = float(dp_clip), float(dp_noise)
         self.dp = self.dp_clip > 0.0
@@ -248,7 +259,8 @@ class FusedTinyTrainer:
             wprep=_lib.ptr(self.wprep), xg=_lib.ptr(self.xg), yg=_lib.ptr(self.yg), L=L, nc=self.nc,
             slab_stride=self.stride, B=self.B, lr=self.lr, momentum=self.momentum, wd=self.wd,
             nesterov=int(self.nesterov), prec=self.prec, dp_clip=self.dp_clip, dp_sigma=self.dp_noise,
-            dp_seed=self.dp_seed, dp_scale=_lib.ptr(self.dp_scale), dp_step=_lib.ptr(self.dp_step))
+            dp_seed=self.dp_seed, dp_scale=_lib.ptr(self.dp_scale), dp_step=_lib.ptr(self.dp_step),
+            xbg=_lib.ptr(self.xbg))
 
     # ------------------------------------------------------------------ graph management
     def _round_of(self, n: int, table: torch.Tensor):

@@ -11,6 +11,10 @@
 // The sample's parameter gradient (1,458 floats for C=2) plus its loss form one row.  The rows of a step are
 // summed and SGD+momentum is applied to the flat fp32 master weights by a second launch
 // (``slab_reduce_sgd_kernel``); a local round's launches are captured into one hipGraph and replayed.
+// The reduce launch of step s also gathers step s + 1's windows (GatherArgs: otherwise idle CUs), both as fp32 rows
+// (xg) and as packed bf16 rows with the conv padding written out as zeros (xbg, kPackLead); a round's steps s > 0 run
+// the PK variant of the step kernel, whose conv1 operand is one 16-byte load of such a row and a one-element shift -
+// conversion, edge shifts and bounds handling are done once per element by the gather, not 7 times per step here.
 // (One launch per step with an in-kernel last-arriver reduction tree and one persistent launch per round were
 // measured slower - 13.23 and 16.33 vs 10.62 us/step, profiles/r4/tiny_phase_diag.txt - and were removed in round 5.)
 //
@@ -60,6 +64,9 @@ __host__ __device__ constexpr int red_dw1(int waves) { return red_m(waves) + msp
 __host__ __device__ constexpr int red_head(int waves) { return red_dw1(waves) + waves * 128; }  // dWh, dbh, loss
 __host__ __device__ constexpr int red_floats(int waves) { return red_head(waves) + 288; }
 
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
 // Write-through (sc1) global accesses for data handed between workgroups inside one launch: the
 // stores need no release fence and the sc1 loads need no acquire fence (MI355X guide, Guideline 16 R1).
 __device__ __forceinline__ void st_wt(__amdgpu_buffer_rsrc_t r, int idx, float v) {
@@ -69,10 +76,25 @@ __device__ __forceinline__ void st_wt4(__amdgpu_buffer_rsrc_t r, int idx, f32x4 
   typedef int i32x4 __attribute__((ext_vector_type(4)));
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), r, idx * 4, 0, 16);
 }
+__device__ __forceinline__ void st_wt_b64(__amdgpu_buffer_rsrc_t r, int byte_off, u32x2 v) {  // 8-byte aligned
+  __builtin_amdgcn_raw_buffer_store_b64(v, r, byte_off, 0, 16);
+}
+__device__ __forceinline__ void st_wt_b16(__amdgpu_buffer_rsrc_t r, int byte_off, unsigned short v) {
+  __builtin_amdgcn_raw_buffer_store_b16(v, r, byte_off, 0, 16);
+}
 __device__ __forceinline__ float ld_wt(__amdgpu_buffer_rsrc_t r, int idx) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, idx * 4, 0, 16));
 }
 constexpr int kOobByte = 0x40000000;  // past every window row (L <= 1024 floats), far from wrapping with + 4j
+
+// Packed bf16 window rows (``xbg``, written by the gather blocks of the reduce launches, read by the PK step kernel):
+//   [kPackLead zeros][bf16(x[0 .. L-1])][zeros up to ldb],  ldb = Lp + 8 (Lp = L rounded up to 32).
+// Step t's conv1 window x[t-3 .. t+3] is elements t + kPackLead - 3 .. t + kPackLead + 3: the zeros on both sides are
+// the conv padding, and the 8-element load of any step t < Lp, which starts at most one element lower, ends at element
+// Lp + kPackLead + 3 < ldb at the latest.  Rows are 16-byte multiples, and a lead of 4 puts x[4j] on an 8-byte
+// boundary (the gather's 4-float form stores 4 bf16 at once).
+constexpr int kPackLead = 4;
+__host__ __device__ constexpr int pack_ldb(int L) { return (L + 31) / 32 * 32 + 8; }
 
 // fp32 path: v_mfma_f32_16x16x4_f32 (exact f32 products, K = 80 = 20 k-steps of 4, no padding)
 constexpr int F32_KSTEPS = C * K2 / 4;
@@ -160,9 +182,10 @@ __device__ __forceinline__ s16x4 lds_tr16(const __bf16* p) {
 //   conv2 dgrad dh1^T[ci][t] = (g W2)[ci][(k,co)] x m[(k,co)][t], times relu'(h1), written over h1
 //   conv1 wgrad dW1ext[ci][kk] = dh1^T[ci][t] x xcol[t][kk]   (both operands by transposing reads; kk = 7 -> db1)
 // The fp32 path keeps conv1 / conv1-wgrad on VALU (exact f32) and the time-major MFMA orientation.
-template <int WAVES, bool F32, bool PF = false>
+template <int WAVES, bool F32, bool PF = false, bool PK = false>
 struct TinySample {
   static_assert(!(PF && F32), "prepared fragments are bf16 operands");
+  static_assert(!PK || PF, "packed window rows feed the prepared-fragment kernel only");
   using AT = std::conditional_t<F32, float, __bf16>;  // activation / MFMA operand type
   static constexpr int NT = WAVES * 64;
   Smem sm;
@@ -272,22 +295,55 @@ struct TinySample {
   // branch, and quarters 1..3 and steps t >= L (whose operand is all zero) load from an out-of-range offset.
   // Offsets never go negative: the three steps t < 3, whose window starts before the row, load x[0 .. 6] and
   // conv1_operand shifts their values into place (tile 0 only: every other wave skips that branch).
-  struct X1 {
+  // PK: the row is a packed bf16 row written by the gather blocks (gather_block, kPackLead) and ``xr`` covers all of it.
+  struct X1f {
     float v[2][K1];
   };
+  struct X1p {
+    u32x4 p[2];  // the 8 packed bf16 of each tile's load
+  };
+  using X1 = std::conditional_t<PK, X1p, X1f>;
   __device__ __forceinline__ int conv1_t(int pi, int u) const {  // (clamped: the pair's second tile may not exist)
     return 16 * min(w + (pi + u) * WAVES, Lp / 16 - 1) + (lane & 15);
   }
   __device__ __forceinline__ void conv1_load(__amdgpu_buffer_rsrc_t xr, int pi, X1& r) const {
+    if constexpr (PK) {
+      // Packed row: step t's window x[t-3 .. t+3] is elements t + 1 .. t + 7 of the row.  One 16-byte
+      // load of the 8 elements from the even element at or below t + 1 (a dword-aligned byte offset, which is all a
+      // raw buffer load of any width needs - the unpacked kernel's x4 + x3 loads start at any float too); the row's
+      // zero pads stand in for the conv padding on both sides, so no offset is clamped and nothing reads past the row.
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int t = conv1_t(pi, u);
-      const int base = (h == 0 && t < L) ? 4 * max(t - 3, 0) : kOobByte;
+      for (int u = 0; u < 2; ++u) {
+        const int t = conv1_t(pi, u);
+        const int off = (h == 0 && t < L) ? 2 * ((t + kPackLead - 3) & ~1) : kOobByte;
+        r.p[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
+      }
+    } else {
 #pragma unroll
-      for (int j = 0; j < K1; ++j) r.v[u][j] = ld_bounded(xr, base + 4 * j);
+      for (int u = 0; u < 2; ++u) {
+        const int t = conv1_t(pi, u);
+        const int base = (h == 0 && t < L) ? 4 * max(t - 3, 0) : kOobByte;
+#pragma unroll
+        for (int j = 0; j < K1; ++j) r.v[u][j] = ld_bounded(xr, base + 4 * j);
+      }
     }
   }
   // The loaded values as the MFMA operand {bf16(x[t-3 .. t+3]), "t < L"} (all zero in quarters 1..3 and for t >= L).
+  // PK: the same operand from the 8 packed bf16 ``d``: the window starts at element 0 or 1 of the load by the
+  // parity of t (the lane's parity: tiles are 16 steps apart), so three funnel shifts move it down and one byte
+  // permute puts the window's last element under the flag.  An out-of-range load is all zero and has no flag.
+  __device__ __forceinline__ bf16x8 conv1_operand_packed(u32x4 d, int t) const {
+    static_assert(kPackLead % 2 == 0, "the shift below assumes an even lead: window start t + kPackLead - 3");
+    const bool odd = !(lane & 1);  // t even: t + kPackLead - 3 is odd, the window starts at element 1
+    const unsigned sh = odd ? 16u : 0u;
+    const unsigned flag = (h == 0 && t < L) ? 0x3f80u : 0u;  // bf16 1.0
+    u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = __builtin_amdgcn_alignbit(d[i + 1], d[i], sh);
+    // bytes {flag.b1, flag.b0, d3 high or low half}
+    o[3] = __builtin_amdgcn_perm(flag, d[3], odd ? 0x05040302u : 0x05040100u);
+    return __builtin_bit_cast(bf16x8, o);
+  }
   __device__ __forceinline__ bf16x8 conv1_operand(const float (&ld)[K1], int t) const {
     float v[K1];
 #pragma unroll
@@ -365,7 +421,10 @@ struct TinySample {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       t[u] = conv1_t(pi, u);
-      Bx[u] = conv1_operand(x.v[u], t[u]);
+      if constexpr (PK)
+        Bx[u] = conv1_operand_packed(x.p[u], t[u]);
+      else
+        Bx[u] = conv1_operand(x.v[u], t[u]);
       // (a clamped duplicate tile rewrites the same values)
       if (h == 0) *reinterpret_cast<bf16x8*>(xcol + t[u] * 8) = Bx[u];
     }
@@ -895,7 +954,9 @@ struct TinySample {
 // MODE 0: full training step (grads -> slab row).  MODE 1: forward only (logits -> out [B, nc]).
 // MODE 2: diagnostic - every workgroup computes its training step twice; the second pass runs with warm
 //         instruction / scalar / data caches (phase stamps of both passes: scripts/diag_step_phases.py).
-template <int WAVES, int MODE, bool F32, bool PF>
+// PK (MODE 0, PF): X holds packed bf16 window rows (kPackLead comment) instead of floats, row b at X + b * ldx
+// (ldx = ldb / 2: the row pitch in 4-byte units, as for float rows).
+template <int WAVES, int MODE, bool F32, bool PF, bool PK = false>
 __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     const float* __restrict__ X, int L, long ldx,        // dataset windows [N, ldx], window length L
     const int* __restrict__ idx,                         // [B] rows of X for this step (nullptr: b)
@@ -905,7 +966,7 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     float inv_B, unsigned long long* __restrict__ stamps,   // stamps: diagnostic phase clock (nullptr = off)
     FusedOpt opt, const unsigned char* __restrict__ wprep) {  // wprep: PF image of ``params`` (PF only)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  TinySample<WAVES, F32, PF> S(smem, L, nc);
+  TinySample<WAVES, F32, PF, PK> S(smem, L, nc);
   constexpr bool TRAIN = MODE != 1;
   const int tid = threadIdx.x;
   const int b = blockIdx.x;
@@ -928,8 +989,9 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     int ylab = 0;
     const long row = idx ? (long)idx[b] : (long)b;
     const float* xrow = X + row * ldx;
-    [[maybe_unused]] const __amdgpu_buffer_rsrc_t xr = make_rsrc(xrow, (long)L * 4);  // exactly the row (bf16)
-    [[maybe_unused]] typename TinySample<WAVES, F32, PF>::X1 x0;
+    // exactly the row (bf16); PK: the whole packed row, pads included
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t xr = make_rsrc(xrow, PK ? ldx * 4 : (long)L * 4);
+    [[maybe_unused]] typename TinySample<WAVES, F32, PF, PK>::X1 x0;
     if constexpr (PF) {
       // conv operands: global image -> VGPRs; only the head's parameters go to LDS (plain fp32 copy)
       S.pf_load_fwd(wprep);
@@ -1026,11 +1088,54 @@ struct GatherArgs {
   int* yg;         // [B]
   int L, ldg, B, vec;  // vec: 16-byte rows (L % 4 == 0, ldx % 4 == 0, X 16-byte aligned)
   int nred;            // blocks below this index reduce; INT_MAX = no gather
+  __bf16* xbg;         // [B][ldb] packed bf16 rows (kPackLead comment), written write-through; nullptr: none
+  int ldb;
 };
 __host__ __device__ inline int gather_rows_per_block(int L, int vec, int nt) {
   const int per_row = vec ? L / 4 : L;
   return per_row >= nt ? 1 : nt / per_row;
 }
+
+// A gather block (blockIdx.x >= ga.nred) of NT threads: ``gather_rows_per_block`` rows of the next step's batch, one
+// element (vec: 4 elements) per thread and pass.  With ``xbg`` each thread also stores the bf16 of what it loaded -
+// the same cast as the step kernel's ecg::to_bf16 - and the row's threads share out its zero pads: the whole packed
+// row is written every time, and X is read once.
+template <int NT>
+__device__ __forceinline__ void gather_block(const GatherArgs& ga) {
+  const int per_row = ga.vec ? ga.L / 4 : ga.L;
+  const int rpb = gather_rows_per_block(ga.L, ga.vec, NT);
+  const int r0 = ((int)blockIdx.x - ga.nred) * rpb;
+  const __amdgpu_buffer_rsrc_t xr = make_rsrc(ga.xg, (long)ga.B * ga.ldg * 4);
+  const __amdgpu_buffer_rsrc_t br = make_rsrc(ga.xbg, ga.xbg ? (long)ga.B * ga.ldb * 2 : 0);
+  const int npad = ga.ldb - ga.L;  // pad elements of a packed row: kPackLead in front, the rest behind the data
+  for (int e = threadIdx.x; e < rpb * per_row; e += NT) {
+    const int lr_ = e / per_row, j = e - lr_ * per_row, b = r0 + lr_;
+    if (b >= ga.B) break;  // e only grows, so every later e is past the batch too
+    const long row = ga.idx[b];
+    if (ga.vec) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(ga.X + row * ga.ldx + 4 * j);
+      st_wt4(xr, b * ga.ldg + 4 * j, v);
+      if (ga.xbg) {  // 8-byte units: 4 | L, kPackLead and ldb, so the pads are npad / 4 whole units
+        bf16x4 p;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) p[q] = ecg::to_bf16(v[q]);
+        st_wt_b64(br, (b * ga.ldb + kPackLead + 4 * j) * 2, __builtin_bit_cast(u32x2, p));
+        for (int u = j; u < npad / 4; u += per_row)
+          st_wt_b64(br, (b * ga.ldb + (u == 0 ? 0 : ga.L + 4 * u)) * 2, u32x2{0u, 0u});
+      }
+    } else {
+      const float v = ga.X[row * ga.ldx + j];
+      st_wt(xr, b * ga.ldg + j, v);
+      if (ga.xbg) {
+        st_wt_b16(br, (b * ga.ldb + kPackLead + j) * 2, __builtin_bit_cast(unsigned short, ecg::to_bf16(v)));
+        for (int u = j; u < npad; u += per_row)
+          st_wt_b16(br, (b * ga.ldb + (u < kPackLead ? u : ga.L + u)) * 2, (unsigned short)0);
+      }
+    }
+    if (j == 0) ga.yg[b] = ga.Y[row];
+  }
+}
+static_assert(kPackLead == 4, "gather_block's 4-float form writes the lead as one 8-byte unit");
 
 template <int RED_COLS>
 __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_sgd_kernel(
@@ -1041,21 +1146,7 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_sgd_kernel(
     GatherArgs ga) {
   constexpr int NT = RED_COLS * RED_ROWG;
   if ((int)blockIdx.x >= ga.nred) {  // block-uniform: gather blocks never reach the barrier below
-    const int per_row = ga.vec ? ga.L / 4 : ga.L;
-    const int rpb = gather_rows_per_block(ga.L, ga.vec, NT);
-    const int r0 = ((int)blockIdx.x - ga.nred) * rpb;
-    const __amdgpu_buffer_rsrc_t xr = make_rsrc(ga.xg, (long)ga.B * ga.ldg * 4);
-    for (int e = threadIdx.x; e < rpb * per_row; e += NT) {
-      const int lr_ = e / per_row, j = e - lr_ * per_row, b = r0 + lr_;
-      if (b >= ga.B) break;  // e only grows, so every later e is past the batch too
-      const long row = ga.idx[b];
-      if (ga.vec) {
-        st_wt4(xr, b * ga.ldg + 4 * j, *reinterpret_cast<const f32x4*>(ga.X + row * ga.ldx + 4 * j));
-      } else {
-        st_wt(xr, b * ga.ldg + j, ga.X[row * ga.ldx + j]);
-      }
-      if (j == 0) ga.yg[b] = ga.Y[row];
-    }
+    gather_block<NT>(ga);
     return;
   }
   __shared__ float part[RED_ROWG][RED_COLS + 1];
@@ -1194,21 +1285,7 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_dp_sgd_kernel
     const unsigned long long* __restrict__ dp_step, GatherArgs ga) {
   constexpr int NT = RED_COLS * RED_ROWG;
   if ((int)blockIdx.x >= ga.nred) {  // block-uniform: gather blocks never reach the barrier below
-    const int per_row = ga.vec ? ga.L / 4 : ga.L;
-    const int rpb = gather_rows_per_block(ga.L, ga.vec, NT);
-    const int r0 = ((int)blockIdx.x - ga.nred) * rpb;
-    const __amdgpu_buffer_rsrc_t xr = make_rsrc(ga.xg, (long)ga.B * ga.ldg * 4);
-    for (int e = threadIdx.x; e < rpb * per_row; e += NT) {
-      const int lr_ = e / per_row, j = e - lr_ * per_row, b = r0 + lr_;
-      if (b >= ga.B) break;  // e only grows, so every later e is past the batch too
-      const long row = ga.idx[b];
-      if (ga.vec) {
-        st_wt4(xr, b * ga.ldg + 4 * j, *reinterpret_cast<const f32x4*>(ga.X + row * ga.ldx + 4 * j));
-      } else {
-        st_wt(xr, b * ga.ldg + j, ga.X[row * ga.ldx + j]);
-      }
-      if (j == 0) ga.yg[b] = ga.Y[row];
-    }
+    gather_block<NT>(ga);
     return;
   }
   __shared__ float part[RED_ROWG][RED_COLS + 1];
@@ -1287,12 +1364,13 @@ struct StepArgs {
   int out_stride, B;
   float inv_B;
   const unsigned char* wprep;  // PF image of ``params`` (bf16 only); nullptr: operands built in LDS from ``params``
+  bool packed = false;  // X holds packed bf16 rows (PK kernel: MODE 0, bf16, wprep; idx == nullptr)
 };
 
-template <int WAVES, int MODE, bool F32, bool PF>
+template <int WAVES, int MODE, bool F32, bool PF, bool PK = false>
 int launch_step(const StepArgs& a, hipStream_t stream) {
   const Smem sm = make_smem(a.L, WAVES, a.nc, F32);
-  auto kern = tiny_ecg_step_kernel<WAVES, MODE, F32, PF>;
+  auto kern = tiny_ecg_step_kernel<WAVES, MODE, F32, PF, PK>;
   if (sm.bytes > 64 * 1024)
     ECG_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, sm.bytes));
   hipLaunchKernelGGL(kern, dim3(a.B), dim3(WAVES * 64), sm.bytes, stream, a.X, a.L, a.ldx, a.idx, a.Y, a.params, a.nc,
@@ -1354,6 +1432,11 @@ int step_dispatch(int mode, int prec, const StepArgs& a, hipStream_t stream) {
   if (st) return st;
   if (a.wprep && prec == 1) return ecg::kBadArg;
   const int waves = pick_waves(a.L, prec == 1);
+  if (a.packed) {
+    if (mode != 0 || prec != 0 || !a.wprep || a.idx) return ecg::kBadArg;
+    return waves == 8 ? launch_step<8, 0, false, true, true>(a, stream)
+                      : launch_step<16, 0, false, true, true>(a, stream);
+  }
   if (prec == 1) return dispatch_cfg<true, false>(mode, waves, a, stream);
   if (a.wprep) return dispatch_cfg<false, true>(mode, waves, a, stream);
   return dispatch_cfg<false, false>(mode, waves, a, stream);
@@ -1551,6 +1634,8 @@ struct EcgTinyRound {
   unsigned long long dp_seed;
   float* dp_scale;
   unsigned long long* dp_step;
+  void* xbg;  // bf16 [2][B][ldb] (ecg_tiny_gather_halfs; nullable, needs xg): the gather also writes each window as
+              // a packed bf16 row into buffer (s + 1) & 1, and step s + 1 runs the kernel that reads those (PK)
 };
 
 ECG_API int ecg_tiny_round_sizeof(void) { return (int)sizeof(EcgTinyRound); }
@@ -1560,6 +1645,7 @@ static int check_round(const EcgTinyRound* r) {
   if (r->prec != 0 && r->prec != 1) return ecg::kBadArg;
   if (r->wprep && r->prec != 0) return ecg::kBadArg;
   if ((!r->xg) != (!r->yg) || (r->xg && (!r->wprep || !r->idx))) return ecg::kBadArg;
+  if (r->xbg && !r->xg) return ecg::kBadArg;
   if (r->dp_clip < 0.f || r->dp_sigma < 0.f || (r->dp_sigma > 0.f && r->dp_clip == 0.f)) return ecg::kBadArg;
   if (r->dp_clip > 0.f && (!r->dp_scale || !r->dp_step)) return ecg::kBadArg;
   return check_step_args(r->L, r->nc, r->B, r->slab_stride, 0, r->prec == 1);
@@ -1574,8 +1660,13 @@ static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
   // Gathered steps (xg/yg): step s > 0 reads ping-pong buffer s & 1, which the reduce launch of step s - 1 filled
   // (stream order: that buffer's previous reader, step s - 2's kernel, finished before that reduce started).
   const int ldg = (r.L + 3) / 4 * 4;
+  // Packed steps (xbg): the same gather also leaves the windows as packed bf16 rows, and step s > 0 reads those
+  // instead of xg (xg is still written: it is the unpacked kernel's input and the record of what was gathered).
+  const int ldb = pack_ldb(r.L);
+  __bf16* xbg = static_cast<__bf16*>(r.xbg);
   GatherArgs ga{r.X, r.ldx, nullptr, r.Y, nullptr, nullptr, r.L, ldg, r.B,
-                (r.L % 4 == 0 && r.ldx % 4 == 0 && reinterpret_cast<uintptr_t>(r.X) % 16 == 0) ? 1 : 0, INT_MAX};
+                (r.L % 4 == 0 && r.ldx % 4 == 0 && reinterpret_cast<uintptr_t>(r.X) % 16 == 0) ? 1 : 0, INT_MAX,
+                nullptr, ldb};
   for (int s = 0; s < r.steps; ++s) {
     const int* idx = r.idx ? r.idx + (long)s * r.B : nullptr;
     const bool gathered = r.xg && s > 0;
@@ -1584,6 +1675,7 @@ static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
       ga.idx = idx + r.B;
       ga.xg = r.xg + (long)((s + 1) & 1) * r.B * ldg;
       ga.yg = r.yg + (long)((s + 1) & 1) * r.B;
+      ga.xbg = xbg ? xbg + (long)((s + 1) & 1) * r.B * ldb : nullptr;
     }
     StepArgs a{r.X, r.L, r.ldx, idx, r.Y, r.params, r.nc, r.slab, r.slab_stride, r.B, 1.0f / (float)r.B,
                s == 0 ? nullptr : wprep};
@@ -1592,6 +1684,11 @@ static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
       a.ldx = ldg;
       a.idx = nullptr;
       a.Y = r.yg + (long)(s & 1) * r.B;
+      if (xbg) {
+        a.X = reinterpret_cast<const float*>(xbg + (long)(s & 1) * r.B * ldb);
+        a.ldx = ldb / 2;
+        a.packed = true;
+      }
     }
     int st = step_dispatch(0, r.prec, a, stream);
     if (st) return st;
@@ -1649,6 +1746,9 @@ ECG_API int ecg_tiny_round_capture(void** handle, const EcgTinyRound* round) {
 
 // Floats of the gather buffer ``xg`` of a round (its ``yg`` holds 2 * B int32).
 ECG_API long ecg_tiny_gather_floats(int L, int B) { return 2L * B * ((L + 3) / 4 * 4); }
+
+// bf16 elements of the packed gather buffer ``xbg`` of a round.
+ECG_API long ecg_tiny_gather_halfs(int L, int B) { return 2L * B * pack_ldb(L); }
 
 ECG_API int ecg_round_graph_launch(void* handle, hipStream_t stream) {
   if (!handle) return ecg::kBadArg;

@@ -10,7 +10,7 @@ import csv
 import statistics
 import sys
 
-KERNEL = "tiny_ecg_step_kernel<16, 0, false, true>"
+KERNEL = "tiny_ecg_step_kernel<16, 0, false, true"  # the PF training step, unpacked or packed (PK) rows
 
 
 def main(path, label="?"):
