@@ -45,7 +45,14 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-f
 # vector issue port): without NaN / signed-zero semantics hipcc drops the canonicalising v_max before every ReLU and
 # the 0 + x seeds of the running sums (-95 static VALU of ~1,800) - 11.02 -> 10.86 us/step at K=500
 # (profiles/r3/tiny_fp_flags_ab.txt).  ReLU of a NaN is 0 either way (v_max_f32 returns the non-NaN operand).
-FILE_FLAGS = {"tiny_ecg_step.hip": ["-fno-honor-nans", "-fno-signed-zeros"]}
+#
+# Kernarg preload, this translation unit only: gfx950 delivers the first kernel-argument dwords in user SGPRs at wave
+# start (14 of them beside the kernarg pointer), so the step and reduce kernels form the addresses of their first
+# loads without a scalar-load round trip; their parameter order is chosen for it (comment at tiny_ecg_step_kernel).
+# The compiler keeps a prologue that loads the same dwords, so the code object also runs where the firmware does not
+# preload.  Measurements: profiles/r10/tiny_kernarg_preload.txt.
+FILE_FLAGS = {"tiny_ecg_step.hip": ["-fno-honor-nans", "-fno-signed-zeros",
+                                    "-mllvm", "-amdgpu-kernarg-preload-count=16"]}
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-pthread"]
 
 

@@ -956,15 +956,30 @@ struct TinySample {
 //         instruction / scalar / data caches (phase stamps of both passes: scripts/diag_step_phases.py).
 // PK (MODE 0, PF): X holds packed bf16 window rows (kPackLead comment) instead of floats, row b at X + b * ldx
 // (ldx = ldb / 2: the row pitch in 4-byte units, as for float rows).
+//
+// Argument order.  This file is built with kernarg preload (csrc/build.py): the hardware places the first 14 dwords of
+// the kernel arguments in SGPRs when the wave starts (16 user SGPRs less the two of the kernarg pointer), and
+// everything behind them is fetched by scalar loads whose wait the compiler puts in front of the first use.  So the
+// arguments come in the order in which the kernel's first instructions need them - the stamps pointer (its null test
+// is the first instruction), then what the addresses of phase 0's loads are made of: the window rows and their
+// pitch, the image, the labels, L, nc and the head parameters - and fill the 14 dwords exactly: X 0-1, ldx 2-3,
+// wprep 4-5, Y 6-7, stamps 8-9, L 10, nc 11, params 12-13.  The slab / logits pointer, its stride and 1/B are first
+// read in phase 3 or later; ``idx`` is first in the kernels that gather for themselves, which run once per round
+// (the PK kernel never reads it).  A pointer or long that straddles dword 14 would not be preloaded at all: keep the
+// 8-byte arguments on even dwords when this list changes.  The code is also correct where the firmware does not
+// preload: the compiler's prologue then loads the same dwords.
 template <int WAVES, int MODE, bool F32, bool PF, bool PK = false>
 __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
-    const float* __restrict__ X, int L, long ldx,        // dataset windows [N, ldx], window length L
-    const int* __restrict__ idx,                         // [B] rows of X for this step (nullptr: b)
+    const float* __restrict__ X, long ldx,               // dataset windows [N, ldx]
+    const unsigned char* __restrict__ wprep,             // PF image of ``params`` (PF only)
     const int* __restrict__ Y,                           // [N] int32 labels (unused in MODE 1)
-    const float* __restrict__ params, int nc,            // flat fp32 params
+    unsigned long long* __restrict__ stamps,             // diagnostic phase clock (nullptr = off)
+    int L, int nc,                                       // window length, classes
+    const float* __restrict__ params,                    // flat fp32 params          -- preloaded up to here
     float* __restrict__ out, int out_stride,             // MODE0/2: slab [B][out_stride]; MODE1: logits
-    float inv_B, unsigned long long* __restrict__ stamps,   // stamps: diagnostic phase clock (nullptr = off)
-    FusedOpt opt, const unsigned char* __restrict__ wprep) {  // wprep: PF image of ``params`` (PF only)
+    float inv_B,
+    const int* __restrict__ idx,                         // [B] rows of X for this step (nullptr: b; PK: unused)
+    int slab_wt) {                                       // FusedOpt::slab_wt
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   TinySample<WAVES, F32, PF, PK> S(smem, L, nc);
   constexpr bool TRAIN = MODE != 1;
@@ -987,12 +1002,27 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     // the pads and head parameters written here are first read after the phase-1 barrier.  Stamp 1 then marks
     // "inputs issued, pads written", not a barrier; the wait for the window is counted in phase 1.
     int ylab = 0;
-    const long row = idx ? (long)idx[b] : (long)b;
+    long row = b;  // PK: gathered rows, read in place (launch_step rejects an idx), so ``idx`` is never waited for
+    if constexpr (!PK) row = idx ? (long)idx[b] : (long)b;
     const float* xrow = X + row * ldx;
     // exactly the row (bf16); PK: the whole packed row, pads included
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t xr = make_rsrc(xrow, PK ? ldx * 4 : (long)L * 4);
     [[maybe_unused]] typename TinySample<WAVES, F32, PF, PK>::X1 x0;
-    if constexpr (PF) {
+    [[maybe_unused]] float hv_pk = 0.f;
+    if constexpr (PK) {
+      // Every address here is made of preloaded arguments and the workgroup / lane ids, so the loads go out in
+      // latency order with no wait between them: the packed window row and the label, which the previous reduce
+      // launch's gather blocks wrote through and which come from beyond the L2, then the image (L2-hot: every
+      // workgroup of an XCD reads the same 6.4 KB), then this thread's head parameter.  (The label is a scalar load:
+      // hipcc places it behind the pad stores below, still ahead of the first wait.)  The head parameter is the
+      // last to arrive and nothing reads its LDS copy before phase 3: it is stored after conv1 (below), so that
+      // conv1 waits for the window and the image only and the pad stores of phase 0 wait for nothing.
+      S.conv1_load(xr, 0, x0);
+      ylab = Y[row];
+      S.pf_load_fwd(wprep);
+      const int i = S.lay.wh + tid;
+      hv_pk = i < S.lay.P ? params[i] : 0.f;
+    } else if constexpr (PF) {
       // conv operands: global image -> VGPRs; only the head's parameters go to LDS (plain fp32 copy)
       S.pf_load_fwd(wprep);
       const int i = S.lay.wh + tid;
@@ -1031,6 +1061,10 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     } else {
       ECG_STAMP(1)
       S.conv1_mfma(xr, x0);
+      if constexpr (PK) {
+        const int i = S.lay.wh + tid;
+        if (i < S.lay.P) S.ps[i] = hv_pk;
+      }
     }
     __syncthreads();
     ECG_STAMP(2)
@@ -1048,9 +1082,9 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     __syncthreads();
     ECG_STAMP(5)
     // phase 5: combine partials, scale by g, write this sample's gradient row (published by the kernel boundary).
-    if (WAVES == 16 && opt.slab_wt && S.lay.P - S.lay.b2 + 1 <= S.NT - 448) {
+    if (WAVES == 16 && slab_wt && S.lay.P - S.lay.b2 + 1 <= S.NT - 448) {
       S.row_store(slab_r, rowbase);
-    } else if (opt.slab_wt) {
+    } else if (slab_wt) {
       for (int i = tid; i <= S.lay.P; i += S.NT) st_wt(slab_r, rowbase + i, S.row_value(i));
     } else {
       for (int i = tid; i <= S.lay.P; i += S.NT) out[rowbase + i] = S.row_value(i);
@@ -1071,7 +1105,16 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
 // Column P carries the per-sample loss (accumulated into loss_acc, never SGD-updated).
 // RED_COLS (columns per block) only changes how columns are grouped into blocks, never a column's summation
 // order (fixed by RED_ROWG and the chunking below), so every width gives bitwise-identical results.
+// Argument order (kernarg preload, see tiny_ecg_step_kernel): the 14 preloaded dwords are what stands between the
+// wave's start and its loads - slab 0-1, params 2-3, mom 4-5, then nred (the reduce / gather branch is the first
+// instruction), G, stride, P, the apply / nesterov flags (one dword) and momentum (dwords 6-11) - and the two scalars
+// of the update, lr and wd (12-13), so that the epilogue behind the barrier starts no scalar load of its own.  The
+// image, loss and gradient-copy pointers are fetched under the slab loads; the gather blocks' GatherArgs, about 80
+// bytes by value, comes last - nothing waits for those blocks.  slab_reduce_dp_sgd_kernel keeps the same order and
+// appends its own arguments.
 constexpr int kRedColsDefault = 32;
+constexpr int kRedApply = 1, kRedNesterov = 2;
+inline int red_flags(int apply, int nesterov) { return (apply ? kRedApply : 0) | (nesterov ? kRedNesterov : 0); }
 constexpr int RED_ROWG = 16;
 
 // Next-step gather riding on the reduce launch: blocks >= nred copy the windows and labels of
@@ -1087,7 +1130,6 @@ struct GatherArgs {
   float* xg;       // [B][ldg] written write-through
   int* yg;         // [B]
   int L, ldg, B, vec;  // vec: 16-byte rows (L % 4 == 0, ldx % 4 == 0, X 16-byte aligned)
-  int nred;            // blocks below this index reduce; INT_MAX = no gather
   __bf16* xbg;         // [B][ldb] packed bf16 rows (kPackLead comment), written write-through; nullptr: none
   int ldb;
 };
@@ -1096,15 +1138,15 @@ __host__ __device__ inline int gather_rows_per_block(int L, int vec, int nt) {
   return per_row >= nt ? 1 : nt / per_row;
 }
 
-// A gather block (blockIdx.x >= ga.nred) of NT threads: ``gather_rows_per_block`` rows of the next step's batch, one
+// A gather block (blockIdx.x >= nred) of NT threads: ``gather_rows_per_block`` rows of the next step's batch, one
 // element (vec: 4 elements) per thread and pass.  With ``xbg`` each thread also stores the bf16 of what it loaded -
 // the same cast as the step kernel's ecg::to_bf16 - and the row's threads share out its zero pads: the whole packed
 // row is written every time, and X is read once.
 template <int NT>
-__device__ __forceinline__ void gather_block(const GatherArgs& ga) {
+__device__ __forceinline__ void gather_block(const GatherArgs& ga, int nred) {
   const int per_row = ga.vec ? ga.L / 4 : ga.L;
   const int rpb = gather_rows_per_block(ga.L, ga.vec, NT);
-  const int r0 = ((int)blockIdx.x - ga.nred) * rpb;
+  const int r0 = ((int)blockIdx.x - nred) * rpb;
   const __amdgpu_buffer_rsrc_t xr = make_rsrc(ga.xg, (long)ga.B * ga.ldg * 4);
   const __amdgpu_buffer_rsrc_t br = make_rsrc(ga.xbg, ga.xbg ? (long)ga.B * ga.ldb * 2 : 0);
   const int npad = ga.ldb - ga.L;  // pad elements of a packed row: kPackLead in front, the rest behind the data
@@ -1139,14 +1181,17 @@ static_assert(kPackLead == 4, "gather_block's 4-float form writes the lead as on
 
 template <int RED_COLS>
 __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_sgd_kernel(
-    const float* __restrict__ slab, int G, int stride, int P,
-    float* __restrict__ params, float* __restrict__ mom, float* __restrict__ grad_out,
-    float* __restrict__ loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
-    unsigned char* __restrict__ wprep,  // wprep: PF image kept current with the updated parameters (nullable)
-    GatherArgs ga) {
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom,
+    int nred,   // blocks below this index reduce, the rest gather; INT_MAX = no gather
+    int G, int stride, int P,
+    int flags,  // kRedApply | kRedNesterov
+    float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep,   // PF image kept current with the updated parameters (nullable)
+    float* __restrict__ loss_acc, float* __restrict__ grad_out, GatherArgs ga) {
   constexpr int NT = RED_COLS * RED_ROWG;
-  if ((int)blockIdx.x >= ga.nred) {  // block-uniform: gather blocks never reach the barrier below
-    gather_block<NT>(ga);
+  const int apply = flags & kRedApply, nesterov = flags & kRedNesterov;
+  if ((int)blockIdx.x >= nred) {  // block-uniform: gather blocks never reach the barrier below
+    gather_block<NT>(ga, nred);
     return;
   }
   __shared__ float part[RED_ROWG][RED_COLS + 1];
@@ -1278,14 +1323,15 @@ __global__ __launch_bounds__(ROWS * 64) void dp_row_scale_kernel(
 // the results are bitwise the plain kernel's.  The loss column is neither scaled nor noised.
 template <int RED_COLS>
 __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_dp_sgd_kernel(
-    const float* __restrict__ slab, int G, int stride, int P,
-    float* __restrict__ params, float* __restrict__ mom, float* __restrict__ grad_out,
-    float* __restrict__ loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
-    unsigned char* __restrict__ wprep, const float* __restrict__ scale, float noise_scale, unsigned long long seed,
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
+    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, float* __restrict__ grad_out,
+    const float* __restrict__ scale, float noise_scale, unsigned long long seed,
     const unsigned long long* __restrict__ dp_step, GatherArgs ga) {
   constexpr int NT = RED_COLS * RED_ROWG;
-  if ((int)blockIdx.x >= ga.nred) {  // block-uniform: gather blocks never reach the barrier below
-    gather_block<NT>(ga);
+  const int apply = flags & kRedApply, nesterov = flags & kRedNesterov;
+  if ((int)blockIdx.x >= nred) {  // block-uniform: gather blocks never reach the barrier below
+    gather_block<NT>(ga, nred);
     return;
   }
   __shared__ float part[RED_ROWG][RED_COLS + 1];
@@ -1373,8 +1419,9 @@ int launch_step(const StepArgs& a, hipStream_t stream) {
   auto kern = tiny_ecg_step_kernel<WAVES, MODE, F32, PF, PK>;
   if (sm.bytes > 64 * 1024)
     ECG_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, sm.bytes));
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(WAVES * 64), sm.bytes, stream, a.X, a.L, a.ldx, a.idx, a.Y, a.params, a.nc,
-                     a.out, a.out_stride, a.inv_B, g_stamps, no_fuse(), PF ? a.wprep : nullptr);
+  if (PK && a.idx) return ecg::kBadArg;  // the PK kernel reads row b
+  hipLaunchKernelGGL(kern, dim3(a.B), dim3(WAVES * 64), sm.bytes, stream, a.X, a.ldx, PF ? a.wprep : nullptr, a.Y,
+                     g_stamps, a.L, a.nc, a.params, a.out, a.out_stride, a.inv_B, a.idx, no_fuse().slab_wt);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -1450,16 +1497,15 @@ int reduce_dispatch(const float* slab, int G, int stride, int P, float* params, 
   constexpr int cols = kRedColsDefault;  // columns per reduction block (A/B: profiles/r1_final/ab_red_cols.txt)
   const int blocks = (P + 1 + cols - 1) / cols;
   GatherArgs ga{};
-  ga.nred = INT_MAX;
-  int grid = blocks;
+  int grid = blocks, nred = INT_MAX;
   if (gather) {
     ga = *gather;
-    ga.nred = blocks;
+    nred = blocks;
     const int rpb = gather_rows_per_block(ga.L, ga.vec, cols * RED_ROWG);
     grid += (ga.B + rpb - 1) / rpb;
   }
-  hipLaunchKernelGGL(slab_reduce_sgd_kernel<cols>, dim3(grid), dim3(cols * RED_ROWG), 0, stream, slab, G, stride, P,
-                     params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply, wprep, ga);
+  hipLaunchKernelGGL(slab_reduce_sgd_kernel<cols>, dim3(grid), dim3(cols * RED_ROWG), 0, stream, slab, params, mom,
+                     nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc, grad_out, ga);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -1491,18 +1537,17 @@ int dp_reduce_dispatch(const float* slab, int G, int stride, int P, float* param
   constexpr int cols = kRedColsDefault;
   const int blocks = (P + 1 + cols - 1) / cols;
   GatherArgs ga{};
-  ga.nred = INT_MAX;
-  int grid = blocks;
+  int grid = blocks, nred = INT_MAX;
   if (gather) {
     ga = *gather;
-    ga.nred = blocks;
+    nred = blocks;
     const int rpb = gather_rows_per_block(ga.L, ga.vec, cols * RED_ROWG);
     grid += (ga.B + rpb - 1) / rpb;
   }
   const float noise_scale = dp.sigma * dp.clip / (float)G;
-  hipLaunchKernelGGL(slab_reduce_dp_sgd_kernel<cols>, dim3(grid), dim3(cols * RED_ROWG), 0, stream, slab, G, stride, P,
-                     params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply, wprep, dp.scale, noise_scale,
-                     dp.seed, dp.step, ga);
+  hipLaunchKernelGGL(slab_reduce_dp_sgd_kernel<cols>, dim3(grid), dim3(cols * RED_ROWG), 0, stream, slab, params, mom,
+                     nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc, grad_out,
+                     dp.scale, noise_scale, dp.seed, dp.step, ga);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -1665,8 +1710,7 @@ static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
   const int ldb = pack_ldb(r.L);
   __bf16* xbg = static_cast<__bf16*>(r.xbg);
   GatherArgs ga{r.X, r.ldx, nullptr, r.Y, nullptr, nullptr, r.L, ldg, r.B,
-                (r.L % 4 == 0 && r.ldx % 4 == 0 && reinterpret_cast<uintptr_t>(r.X) % 16 == 0) ? 1 : 0, INT_MAX,
-                nullptr, ldb};
+                (r.L % 4 == 0 && r.ldx % 4 == 0 && reinterpret_cast<uintptr_t>(r.X) % 16 == 0) ? 1 : 0, nullptr, ldb};
   for (int s = 0; s < r.steps; ++s) {
     const int* idx = r.idx ? r.idx + (long)s * r.B : nullptr;
     const bool gathered = r.xg && s > 0;
