@@ -50,6 +50,13 @@ class FedAvgConfig:
     dp_noise: float = 0.0
     dp_delta: float = 1e-5
     privacy_csv: str = "results/fedavg_privacy.csv"
+    # client sampling (off by default; TinyECG on the fused or torch backend): every GPU holds clients_per_gpu virtual
+    # clients (contiguous partitions of its training windows); each round a cohort of them (0: all) is drawn, trains
+    # from the global weights with batches of batch_size, and their mean is this GPU's contribution to FedAvg; rank 0
+    # appends the cohort's shape per round to cohort_csv
+    clients_per_gpu: int = 1
+    cohort: int = 0
+    cohort_csv: str = "results/fedavg_cohort.csv"
     results_csv: str = "results/fedavg_results.csv"
     jsonl: Optional[str] = None
     model: str = "tiny_ecg"

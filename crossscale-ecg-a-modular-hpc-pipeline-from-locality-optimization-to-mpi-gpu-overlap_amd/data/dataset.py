@@ -13,6 +13,8 @@ MI355X-first additions:
   * ``DeviceIndexSampler`` produces the same epoch/drop-last batch order as ``make_gpu_batch_iter`` but as
     a static int32 index table ``[steps, B]`` on the device, which the fused HIP train step gathers from
     directly (no per-step gather kernel, graph-capturable).
+  * ``CohortSampler`` partitions the windows among virtual clients and draws, per FedAvg round, a cohort of clients
+    and their batches as one ``[steps, cohort * B]`` table - a pure function of ``(seed, round)``.
   * ``labels="parity"`` gives a learnable synthetic label (sign of the window mean) for convergence tests.
 """
 from __future__ import annotations
@@ -256,3 +258,58 @@ class DeviceIndexSampler:
     def next_batch(self) -> torch.Tensor:
         t = torch.empty((1, self.B), dtype=torch.int32, device=self.device)
         return self.fill(t)[0]
+
+
+class CohortSampler:
+    """Client sampling for cohorts of virtual clients: which clients train in round ``r``, and on which rows.
+
+    The ``n_windows`` training windows are split into ``clients`` contiguous partitions of ``n = n_windows // clients``
+    rows (client k owns rows ``[k * n, (k + 1) * n)``; a remainder at the end is unused).  Round ``r`` draws ``cohort``
+    distinct clients with a host generator seeded from ``mix64(seed) ^ r`` and, for each of them, ``steps * B`` rows of
+    its partition: consecutive slices of fresh random permutations of the partition (no row twice within one pass
+    over the partition; a new permutation starts where one runs out, also in the middle of a batch), produced on the
+    device by one batched ``argsort`` of random keys like ``DeviceIndexSampler``'s, from a device generator seeded from
+    the same pair.  ``fill`` writes them as the table ``[steps][cohort * B]``, client j of the cohort in columns
+    ``[j * B, (j + 1) * B)``.
+
+    The sampler holds no state between rounds: a run resumed at round r draws what the uninterrupted run drew.
+    """
+
+    def __init__(self, n_windows: int, batch_size: int, steps: int, clients: int, cohort: int, device,
+                 seed: Optional[int] = None):
+        if clients < 1 or not 1 <= cohort <= clients:
+            raise ValueError(f"need 1 <= cohort <= clients, got cohort {cohort} of {clients} clients")
+        self.N, self.B, self.S, self.K, self.M = int(n_windows), int(batch_size), int(steps), int(clients), int(cohort)
+        self.n = self.N // self.K
+        if self.n < self.B:
+            raise RuntimeError(f"{self.N} windows over {self.K} clients leave {self.n} per client < batch {self.B}")
+        self.device = torch.device(device)
+        self.seed = 0 if seed is None else int(seed)
+        self.passes = (self.S * self.B + self.n - 1) // self.n  # permutations of a partition per client and round
+
+    def _round_seed(self, r: int) -> int:
+        from ..utils.philox import mix64
+        return mix64(self.seed) ^ int(r)
+
+    def clients_of(self, r: int) -> List[int]:
+        """The cohort of round ``r``: ``cohort`` distinct client ids, in the order of their table columns."""
+        g = torch.Generator()
+        g.manual_seed(self._round_seed(r))
+        return torch.randperm(self.K, generator=g)[: self.M].tolist()
+
+    def fill(self, r: int, table: torch.Tensor) -> List[int]:
+        """Write round ``r``'s batches into ``table`` (int32 ``[steps, cohort * B]``) in place; returns the cohort."""
+        if table.dtype != torch.int32 or tuple(table.shape) != (self.S, self.M * self.B):
+            raise ValueError(f"index table must be int32 [{self.S}, {self.M * self.B}], got {table.dtype} "
+                             f"{tuple(table.shape)}")
+        from ..utils.philox import mix64
+        ids = self.clients_of(r)
+        g = torch.Generator(device=self.device)
+        g.manual_seed(mix64(self._round_seed(r)))
+        keys = torch.randint(0, 1 << 62, (self.M, self.passes, self.n), device=self.device, generator=g,
+                             dtype=torch.int64)
+        rows = keys.argsort(dim=2).reshape(self.M, self.passes * self.n)[:, : self.S * self.B]
+        rows = rows + (torch.tensor(ids, dtype=torch.int64) * self.n).to(self.device)[:, None]
+        # [M, S, B] -> [S, M, B]: a step's row holds the clients' batches back to back
+        table.copy_(rows.view(self.M, self.S, self.B).permute(1, 0, 2).reshape(self.S, self.M * self.B))
+        return ids

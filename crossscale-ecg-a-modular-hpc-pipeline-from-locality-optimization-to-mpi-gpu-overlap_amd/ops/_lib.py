@@ -70,6 +70,14 @@ class TinyRound(C.Structure):
                 ("xbg", vp)]
 
 
+class TinyCohortRound(C.Structure):
+    """``EcgTinyCohortRound`` of csrc/kernels/tiny_ecg_step.hip, field for field (a null pointer is ``None``)."""
+    _fields_ = [("X", vp), ("ldx", i64), ("idx", vp), ("Y", vp), ("params", vp), ("mom", vp), ("slab", vp),
+                ("loss_acc", vp), ("wprep", vp), ("xg", vp), ("yg", vp), ("xbg", vp), ("global_params", vp),
+                ("L", i32), ("nc", i32), ("slab_stride", i32), ("B", i32), ("steps", i32), ("M", i32),
+                ("fanout", i32), ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32)]
+
+
 def _bind_kernels(lib: C.CDLL) -> None:
     _sig(lib, "ecg_tiny_param_count", [i32])
     _sig(lib, "ecg_tiny_smem_bytes", [i32, i32])
@@ -90,6 +98,14 @@ def _bind_kernels(lib: C.CDLL) -> None:
                           "ops/_lib.py: rebuild the library (python csrc/build.py) or update TinyRound")
     _sig(lib, "ecg_tiny_round_enqueue", [C.POINTER(TinyRound), vp])
     _sig(lib, "ecg_tiny_round_capture", [C.POINTER(vp), C.POINTER(TinyRound)])
+    native = _sig(lib, "ecg_tiny_cohort_round_sizeof", [])()
+    if native != C.sizeof(TinyCohortRound):
+        raise NativeError(f"EcgTinyCohortRound is {native} bytes in libecg_kernels.so but {C.sizeof(TinyCohortRound)} "
+                          "in ops/_lib.py: rebuild the library (python csrc/build.py) or update TinyCohortRound")
+    _sig(lib, "ecg_tiny_cohort_round_enqueue", [C.POINTER(TinyCohortRound), vp])
+    _sig(lib, "ecg_tiny_cohort_round_capture", [C.POINTER(vp), C.POINTER(TinyCohortRound)])
+    _sig(lib, "ecg_tiny_cohort_param_stride", [i32])
+    _sig(lib, "ecg_tiny_cohort_wprep_stride", [])
     _sig(lib, "ecg_tiny_gather_floats", [i32, i32], i64)
     _sig(lib, "ecg_tiny_gather_halfs", [i32, i32], i64)
     _sig(lib, "ecg_tiny_step_grads_twice", [vp, i32, i64, vp, vp, vp, i32, vp, i32, i32, f32, i32, vp, vp])

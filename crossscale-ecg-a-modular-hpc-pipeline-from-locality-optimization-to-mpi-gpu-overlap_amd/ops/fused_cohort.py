@@ -1,0 +1,219 @@
+"""Cohorts of virtual FedAvg clients on one GPU (Python side of the cohort entries of csrc/kernels/tiny_ecg_step.hip).
+
+The fused step kernel runs one workgroup per window, so a client with a small batch leaves most of the GPU idle.
+``FusedCohortTrainer`` holds ``clients`` virtual clients (contiguous partitions of its windows) and trains a
+``cohort`` of them per round side by side: a fan-out of the global weights, then per step ONE step launch over the
+cohort's ``cohort * B`` windows and ONE reduce + SGD launch over its clients, then the clients' mean in ascending
+cohort order into the global weights - captured into one hipGraph like a single client's round.  Virtual clients keep
+no state between rounds (weights from the global model, zero momentum), and which clients and rows a round uses is a
+pure function of ``(seed, round)`` (``data.dataset.CohortSampler``).  Limits: no DP-SGD in a cohort, equal client
+sizes, plain (unweighted) mean.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import List, Optional
+
+import torch
+
+from . import _lib
+from ..data.dataset import CohortSampler
+from ..models.tiny_ecg import TinyECG, num_params
+from .fused_tiny import _check_dataset, labels_int32, prec_id, slab_stride
+from .tiny_eval import EvalResult, TinyEvaluator, tiny_evaluate
+
+
+class FusedCohortTrainer:
+    """``cohort`` of ``clients`` virtual clients per round on the fused HIP step; the trainer interface of
+    ``FusedTinyTrainer``.  ``params`` is the model's flat buffer: the global weights that FedAvg all-reduces."""
+
+    def __init__(self, model: TinyECG, x_gpu: torch.Tensor, y_gpu: torch.Tensor, batch_size: int,
+                 steps_per_round: int, clients: int, cohort: Optional[int] = None, lr: float = 1e-2,
+                 momentum: float = 0.9, weight_decay: float = 0.0, nesterov: bool = False, seed: Optional[int] = None,
+                 use_graph: Optional[bool] = None, precision: str = "bf16", dp_clip: float = 0.0):
+        if dp_clip > 0.0:
+            raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients: the cohort "
+                             "reduce has no per-sample clip")
+        self.device = x_gpu.device
+        self.precision = precision
+        self.prec = prec_id(precision)
+        self.model = model
+        self.nc = model.num_classes
+        self.params = model.flat if model.flat is not None else model.flatten_parameters()
+        if self.params.device != self.device:
+            raise ValueError("model and dataset must be on the same device")
+        self.P = num_params(self.nc)
+        self.x = x_gpu.contiguous()
+        self.y32 = labels_int32(y_gpu, self.nc)
+        _check_dataset(self.x, self.y32, self.nc)
+        self.B, self.S = int(batch_size), int(steps_per_round)
+        self.K = int(clients)
+        self.M = self.K if not cohort else int(cohort)
+        self.lr, self.momentum, self.wd, self.nesterov = float(lr), float(momentum), float(weight_decay), bool(nesterov)
+        self.sampler = CohortSampler(self.x.shape[0], self.B, self.S, self.K, self.M, self.device, seed=seed)
+        lib = _lib.kernels()
+        L = self.x.shape[1]
+        if lib.ecg_tiny_smem_bytes(L, self.prec) > 160 * 1024:
+            raise ValueError(f"window length {L} too long for the fused kernel")
+        rows = self.M * self.B
+        self.stride = slab_stride(self.nc)
+        self.pstride = lib.ecg_tiny_cohort_param_stride(self.nc)
+        self.wstride = lib.ecg_tiny_cohort_wprep_stride()
+        f32 = dict(dtype=torch.float32, device=self.device)
+        # per-client scratch of a round: weights, momenta, images (zero-initialised: the K-padding slots of an image
+        # are never written by the SGD epilogue), gradient rows, loss words
+        self.cparams = torch.zeros(self.M * self.pstride, **f32)
+        self.cmom = torch.zeros(self.M * self.pstride, **f32)
+        self.slab = torch.empty((rows, self.stride), **f32)
+        self.loss_acc = torch.zeros(self.M, **f32)
+        self.wprep = self.xg = self.yg = self.xbg = None
+        if precision == "bf16":
+            self.wprep = torch.zeros(self.M * self.wstride, dtype=torch.uint8, device=self.device)
+            self.xg = torch.zeros(lib.ecg_tiny_gather_floats(L, rows), **f32)
+            self.yg = torch.zeros(2 * rows, dtype=torch.int32, device=self.device)
+            self.xbg = torch.zeros(lib.ecg_tiny_gather_halfs(L, rows), dtype=torch.bfloat16, device=self.device)
+        self.idx_table = torch.zeros((self.S, rows), dtype=torch.int32, device=self.device)
+        self.idx_stage = torch.zeros((self.S, rows), dtype=torch.int32, device=self.device)
+        self._staged: Optional[int] = None
+        self._staged_clients: List[int] = []
+        self.round_clients: List[int] = []  # the cohort of the last round taken
+        self.cohort_round = 0  # rounds taken so far = the round the next staging draws
+        self._loss_steps = 0
+        self.steps_done = 0
+        self.use_graph = (os.environ.get("ECG_TINY_GRAPH", "1") != "0") if use_graph is None else bool(use_graph)
+        self._graphs = {}
+        self._evaluator: Optional[TinyEvaluator] = None
+        self._round = _lib.TinyCohortRound(
+            X=self.x.data_ptr(), ldx=self.x.stride(0), Y=self.y32.data_ptr(), params=self.cparams.data_ptr(),
+            mom=self.cmom.data_ptr(), slab=self.slab.data_ptr(), loss_acc=self.loss_acc.data_ptr(),
+            wprep=_lib.ptr(self.wprep), xg=_lib.ptr(self.xg), yg=_lib.ptr(self.yg), xbg=_lib.ptr(self.xbg),
+            global_params=self.params.data_ptr(), L=L, nc=self.nc, slab_stride=self.stride, B=self.B, M=self.M,
+            fanout=1, lr=self.lr, momentum=self.momentum, wd=self.wd, nesterov=int(self.nesterov), prec=self.prec)
+
+    # ------------------------------------------------------------------ graph management
+    def _round_of(self, n: int, table: torch.Tensor):
+        r = self._round
+        r.idx, r.steps = table.data_ptr(), n
+        return C.byref(r)
+
+    def _graph_for(self, n: int, table: torch.Tensor) -> C.c_void_p:
+        key = (n, table.data_ptr())
+        g = self._graphs.get(key)
+        if g is None:
+            g = C.c_void_p()
+            torch.cuda.synchronize(self.device)
+            _lib.check(_lib.kernels().ecg_tiny_cohort_round_capture(C.byref(g), self._round_of(n, table)),
+                       "ecg_tiny_cohort_round_capture")
+            self._graphs[key] = g
+        return g
+
+    def close(self):
+        graphs, self._graphs = getattr(self, "_graphs", {}), {}
+        for g in graphs.values():
+            if g.value:
+                _lib.kernels().ecg_round_graph_destroy(g)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ execution
+    def prepare(self, sizes) -> None:
+        """Capture, upload and warm every round graph whose step count is in ``sizes`` (on both index tables).  The
+        warm-up replays are rolled back: global weights, loss words, tables and the round counter stay as found (the
+        per-client buffers are scratch that every round's fan-out rewrites)."""
+        if not self.use_graph:
+            return
+        lib = _lib.kernels()
+        sizes = [self._check_n(n) for n in sizes]
+        state = (self.params, self.loss_acc, self.idx_stage, self.idx_table)
+        snap = [t.clone() for t in state]
+        stream = _lib.stream_ptr(self.device)
+        for n in sizes:
+            for table in (self.idx_stage, self.idx_table):
+                g = self._graph_for(n, table)
+                _lib.check(lib.ecg_round_graph_upload(g, stream), "ecg_round_graph_upload")
+                _lib.check(lib.ecg_round_graph_launch(g, stream), "ecg_round_graph_launch")
+        for t, v in zip(state, snap):
+            t.copy_(v)
+        torch.cuda.synchronize(self.device)
+
+    def _check_n(self, n_steps: Optional[int]) -> int:
+        n = self.S if n_steps is None else int(n_steps)
+        if not 0 < n <= self.S:
+            raise ValueError(f"n_steps must be in [1, {self.S}]")
+        return n
+
+    def set_cohort_round(self, r: int) -> None:
+        """Continue at round ``r`` (checkpoint resume): the next staging draws that round's cohort."""
+        if self._staged is not None:
+            raise RuntimeError("a round is staged: set the round counter before staging")
+        self.cohort_round = int(r)
+
+    def stage(self, n_steps: Optional[int] = None) -> None:
+        """Draw the next round's cohort and batches into the staging table (a round of ``n_steps`` < S steps reads
+        the first ``n_steps`` rows of the table the sampler draws for a full round)."""
+        n = self._check_n(n_steps)
+        self._staged_clients = self.sampler.fill(self.cohort_round, self.idx_stage)
+        self._staged = n
+
+    def prepare_round(self, n_steps: Optional[int] = None, reset_loss: bool = True) -> None:
+        n = self._check_n(n_steps)
+        if reset_loss:
+            self.loss_acc.zero_()
+            self._loss_steps = 0
+        if self._staged != n:
+            if self._staged is not None:
+                raise RuntimeError(f"{self._staged} rows are staged for the next round, not {n}")
+            self.stage(n)
+
+    def take_staged(self, n_steps: Optional[int] = None) -> torch.Tensor:
+        n = self._check_n(n_steps)
+        if self._staged != n:
+            raise RuntimeError("launch_round without prepare_round: no batches staged for this round")
+        self._staged = None
+        self.idx_table, self.idx_stage = self.idx_stage, self.idx_table
+        self.round_clients = self._staged_clients
+        self.cohort_round += 1
+        self.steps_done += n
+        self._loss_steps += n
+        return self.idx_table
+
+    def run_round(self, n_steps: Optional[int] = None, reset_loss: bool = True, next_n: Optional[int] = None) -> None:
+        self.prepare_round(n_steps, reset_loss)
+        self.launch_round(n_steps, next_n)
+
+    def launch_round(self, n_steps: Optional[int] = None, next_n: Optional[int] = None) -> None:
+        n = self._check_n(n_steps)
+        table = self.take_staged(n)
+        stream = _lib.stream_ptr(self.device)
+        if self.use_graph:
+            _lib.check(_lib.kernels().ecg_round_graph_launch(self._graph_for(n, table), stream),
+                       "ecg_round_graph_launch")
+        else:
+            _lib.check(_lib.kernels().ecg_tiny_cohort_round_enqueue(self._round_of(n, table), stream),
+                       "ecg_tiny_cohort_round_enqueue")
+        if next_n is not None:
+            self.stage(next_n)
+
+    def evaluate(self, x: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None) -> EvalResult:
+        """Loss / accuracy / confusion matrix of the GLOBAL weights (``FusedTinyTrainer.evaluate``'s contract: reads
+        the weights only, leaves the training state as it was)."""
+        if (x is None) != (y is None):
+            raise ValueError("evaluate takes both windows and labels, or neither")
+        if x is None:
+            x, y32 = self.x, self.y32
+        else:
+            y32 = y if y.dtype == torch.int32 else labels_int32(y, self.nc)
+        if self.precision != "bf16":
+            return tiny_evaluate(self.params, x, y32, None, self.nc, self.precision)
+        if self._evaluator is None:
+            self._evaluator = TinyEvaluator(self.device, self.nc)
+        return self._evaluator.run(self.params, x, y32)
+
+    def avg_loss(self) -> float:
+        """Mean per-sample loss over the cohort's clients and the steps since the last reset (synchronises)."""
+        return float(self.loss_acc.sum().item()) / (self.M * self.B * max(1, self._loss_steps))

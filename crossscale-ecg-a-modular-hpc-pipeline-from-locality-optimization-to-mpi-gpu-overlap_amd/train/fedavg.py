@@ -33,6 +33,14 @@ MI355X execution (vs the reference's host-staged per-tensor MPI calls and per-st
     (``utils.privacy``: the Poisson-subsampling bound at ``sample_rate = batch / training windows``, an approximation
     for the epoch-permutation sampler used here) and rank 0 appends the rows to ``--privacy-csv``.  The training loss in
     the round rows is computed from unclipped, un-noised per-sample losses: it is not private.
+  * ``--clients-per-gpu K`` / ``--cohort M``: client sampling.  Every GPU holds K virtual clients (contiguous
+    partitions of its training windows, after the evaluation hold-out); each round M of them (default K) are drawn as a
+    function of (seed + 7919 * rank, round), train from the global weights with zero momentum on batches of
+    ``--batch-size`` windows, and their mean is what the GPU contributes to FedAvg.  The fused backend trains the
+    whole cohort in one step launch and one reduce launch per step (``ops.fused_cohort``); ``train.cohort`` is the
+    eager reference.  ``samples_per_s`` counts all M * B * S windows of a round; ``batch_size`` in the round rows stays
+    the per-client B; rank 0 appends the cohort's shape per round to ``--cohort-csv``.  TinyECG only; not combined
+    with DP-SGD, ``--sync ddp``, ``--drop-prob`` (client sampling replaces it) or ``--overlap delayed``.
 """
 from __future__ import annotations
 
@@ -56,7 +64,8 @@ from ..parallel.overlap import CommRecord, FedAvgComm, FedAvgRound
 from ..utils import profiling, usable_cpus
 from ..utils.ckpt import (ckpt_path, save_checkpoint, load_checkpoint, latest_checkpoint, rank_state_path,
                           save_rank_state, load_trainer_local_state)
-from ..utils.csvio import RoundStats, append_results, ROUND_COLUMNS, EVAL_COLUMNS, PRIVACY_COLUMNS
+from ..utils.csvio import (RoundStats, append_results, ROUND_COLUMNS, EVAL_COLUMNS, PRIVACY_COLUMNS,
+                           COHORT_COLUMNS)
 from ..utils.philox import mix64
 from ..utils.privacy import epsilon as dp_epsilon
 from ..utils.log import RankLogger
@@ -164,9 +173,52 @@ def check_dp_config(cfg: FedAvgConfig, config_name: str, backend: str) -> None:
             if backend == "fused" else "per-sample gradients bypass DistributedDataParallel's gradient hooks"))
 
 
+def cohort_size(cfg: FedAvgConfig) -> int:
+    """Clients trained per GPU and round: 1 without client sampling, else ``--cohort`` (default: all K)."""
+    if cfg.clients_per_gpu <= 1:
+        return 1
+    return cfg.cohort if cfg.cohort else cfg.clients_per_gpu
+
+
+def check_cohort_config(cfg: FedAvgConfig, backend: str) -> None:
+    """Client sampling (--clients-per-gpu K > 1) exists for TinyECG on the fused and torch backends, exact FedAvg."""
+    K, M = cfg.clients_per_gpu, cfg.cohort
+    if K < 1 or M < 0:
+        raise ValueError("--clients-per-gpu must be >= 1 and --cohort >= 0")
+    if M > K:
+        raise ValueError(f"--cohort {M} exceeds --clients-per-gpu {K}: a cohort is drawn without replacement")
+    if K == 1:
+        return
+    if backend == "hip" or cfg.model != "tiny_ecg":
+        raise ValueError("client sampling (--clients-per-gpu) is implemented for TinyECG, not for ResNet1D models")
+    if cfg.dp_clip > 0:
+        raise ValueError("client sampling (--clients-per-gpu) does not support DP-SGD (--dp-clip): the cohort reduce "
+                         "has no per-sample clip")
+    if cfg.sync == "ddp":
+        raise ValueError("client sampling (--clients-per-gpu) does not support --sync ddp: virtual clients are "
+                         "averaged per round, not per step")
+    if cfg.drop_prob > 0:
+        raise ValueError("client sampling (--clients-per-gpu) replaces --drop-prob: draw a smaller --cohort instead")
+    if cfg.overlap == "delayed":
+        raise ValueError("client sampling (--clients-per-gpu) does not support --overlap delayed: every cohort "
+                         "starts from the averaged weights of the round before")
+
+
 def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistContext, backend: str):
     seed = cfg.seed + 7919 * ctx.rank
     check_dp_config(cfg, config_name, backend)
+    check_cohort_config(cfg, backend)
+    if cfg.clients_per_gpu > 1:
+        kw = dict(clients=cfg.clients_per_gpu, cohort=cohort_size(cfg), lr=cfg.lr, momentum=cfg.momentum, seed=seed)
+        if backend == "fused":
+            from ..ops.fused_cohort import FusedCohortTrainer
+            prec = "bf16" if (config_name == "G1" and cfg.amp_dtype == "bf16") else "fp32"
+            return FusedCohortTrainer(model, x, y, cfg.batch_size, cfg.local_steps, precision=prec, **kw)
+        from .cohort import TorchCohortTrainer
+        if config_name == "G1" and cfg.amp_dtype == "fp16":
+            raise ValueError("client sampling (--clients-per-gpu) on the torch backend runs fp32 or bf16 AMP, not fp16")
+        return TorchCohortTrainer(model, x, y, cfg.batch_size, cfg.local_steps,
+                                  amp_dtype=None if config_name == "G0" else _amp(cfg), **kw)
     dp = dict(dp_clip=cfg.dp_clip, dp_noise=cfg.dp_noise, dp_seed=mix64(seed))
     if backend == "fused":
         from ..ops.fused_tiny import FusedTinyTrainer
@@ -284,6 +336,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
     configs = ["G0", "G1"] if cfg.config == "both" else [cfg.config]
     for cname in configs:  # an unsupported DP-SGD combination stops the run before any configuration trains
         check_dp_config(cfg, cname, pick_backend(cfg, cname, ctx))
+        check_cohort_config(cfg, pick_backend(cfg, cname, ctx))
+    M = cohort_size(cfg)  # clients trained per GPU and round (1: no client sampling)
     all_rows: List[Dict] = []
     fcomm = FedAvgComm(ctx)
     for cname in configs:
@@ -296,6 +350,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         trainer = make_trainer(cfg, cname, model, x, y, ctx, backend)
         log.info(f"[fedavg] {cname}: kernel backend {backend}")
         start_round = _resume(cfg, cname, ctx, comm, model, trainer, log) if cfg.resume else 0
+        if hasattr(trainer, "set_cohort_round"):  # the cohort sampler is a function of (seed, round): no other state
+            trainer.set_cohort_round(start_round)
         fedavg = cfg.sync == "fedavg" and ctx.distributed
         weighted = fedavg and cfg.drop_prob > 0
         mode = cfg.overlap if (fedavg and not weighted) else "none"
@@ -307,6 +363,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         recs = []
         evals = []  # (round, summed record, this rank's eval_ms) per evaluated round
         privacy = []  # DP-SGD: this client's cumulative (round, steps, epsilon)
+        cohorts = []  # client sampling: (round, this rank's drawn client ids)
         sample_rate = cfg.batch_size / x.shape[0]
         for r in range(start_round, cfg.rounds):
             t_round0 = time.perf_counter()
@@ -339,6 +396,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                 if seg_tail:  # the round's last step, its segment all-reduces overlapping its own backward
                     trainer.tail_fedavg(fcomm, rec)
             m_l1 = fcomm.mark()
+            if cfg.clients_per_gpu > 1:
+                cohorts.append((r, list(trainer.round_clients)))
             if cfg.dp_clip > 0:
                 privacy.append((r, trainer.dp_steps,
                                 dp_epsilon(cfg.dp_noise, sample_rate, trainer.dp_steps, cfg.dp_delta)))
@@ -381,7 +440,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
             local_ms = m_l0.ms_to(m_l1) - sum(a.ms_to(b) for a, b in inner)
             row = RoundStats(config=cname, world_size=ctx.world_size, rank=ctx.rank, round_idx=r,
                              batch_size=cfg.batch_size, local_steps=cfg.local_steps, local_train_ms=local_ms,
-                             comm_ms=rec.comm_ms(), samples_per_s=cfg.batch_size * cfg.local_steps / (local_ms / 1e3),
+                             comm_ms=rec.comm_ms(), samples_per_s=M * cfg.batch_size * cfg.local_steps / (local_ms / 1e3),
                              avg_loss=avg_loss, comm_exposed_ms=rec.exposed_ms(), round_wall_ms=wall_ms,
                              backend=backend, overlap=(cfg.overlap if not weighted else "none")
                              if cfg.sync == "fedavg" else cfg.sync)
@@ -418,18 +477,28 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                          f"{last['sample_rate']:.4g}, sigma={cfg.dp_noise:g}, C={cfg.dp_clip:g}) epsilon <= "
                          f"{last['epsilon']:.4g} at delta={cfg.dp_delta:g} (Poisson-sampling bound; the training "
                          "loss is not private)")
+        if cohorts and ctx.rank == 0:
+            crows = [{"config": cname, "world_size": ctx.world_size, "round_idx": r,
+                      "clients_per_gpu": cfg.clients_per_gpu, "cohort": M, "batch_size": cfg.batch_size,
+                      "windows_per_round_per_gpu": M * cfg.batch_size * cfg.local_steps,
+                      "clients_rank0": " ".join(str(c) for c in ids)} for r, ids in cohorts]
+            if cfg.cohort_csv:
+                append_results(crows, cfg.cohort_csv, COHORT_COLUMNS)
+            for row in crows:
+                log.event("cohort", **row)
         gathered = comm.gather(rows, root=0)
         if ctx.rank == 0:
             flat_rows = [row for rl in gathered for row in rl]
             all_rows.extend(flat_rows)
             if cfg.results_csv:
                 append_results(flat_rows, cfg.results_csv, ROUND_COLUMNS)
-            summarize(flat_rows, cname, ctx.world_size, log)
+            summarize(flat_rows, cname, ctx.world_size, log, cohort=M)
         barrier(ctx)
     return all_rows
 
 
-def summarize(rows: List[Dict], cname: str, world: int, log: RankLogger) -> Dict[str, float]:
+def summarize(rows: List[Dict], cname: str, world: int, log: RankLogger, cohort: int = 1) -> Dict[str, float]:
+    """``cohort``: clients trained per GPU and round - a row's windows are cohort * batch_size * local_steps."""
     if not rows:
         return {}
     rounds = sorted({r["round_idx"] for r in rows})
@@ -438,7 +507,7 @@ def summarize(rows: List[Dict], cname: str, world: int, log: RankLogger) -> Dict
     for ri in rounds:
         rr = [r for r in rows if r["round_idx"] == ri]
         wall = max(r["round_wall_ms"] for r in rr) / 1e3
-        node += sum(r["batch_size"] * r["local_steps"] for r in rr) / wall
+        node += sum(cohort * r["batch_size"] * r["local_steps"] for r in rr) / wall
     node /= len(rounds)
     comm = float(np.mean([r["comm_ms"] for r in rows]))
     local = float(np.mean([r["local_train_ms"] for r in rows]))

@@ -61,6 +61,8 @@ EVAL_COLUMNS = ["config", "world_size", "round_idx", "windows", "loss", "accurac
 PRIVACY_COLUMNS = ["config", "world_size", "round_idx", "steps", "sample_rate", "noise_multiplier", "clip_norm",
                    "delta", "epsilon"]
 
+COHORT_COLUMNS = ["config", "world_size", "round_idx", "clients_per_gpu", "cohort", "batch_size",
+                  "windows_per_round_per_gpu", "clients_rank0"]
 LOCALITY_COLUMNS = ["config", "batch_size", "pin_memory", "contiguous", "non_blocking", "data_ms", "h2d_ms",
                     "compute_ms", "step_ms", "samples_per_s"]
 LABL_COLUMNS = ["config", "batch_size", "step_ms", "samples_per_s", "data_ms", "h2d_ms", "compute_ms"]

@@ -968,6 +968,14 @@ struct TinySample {
 // (the PK kernel never reads it).  A pointer or long that straddles dword 14 would not be preloaded at all: keep the
 // 8-byte arguments on even dwords when this list changes.  The code is also correct where the firmware does not
 // preload: the compiler's prologue then loads the same dwords.
+// MODE 3: MODE 0 for a cohort of M virtual clients of B windows each in one launch, grid (B, M).  Workgroup (x, c)
+//         works on row c * B + x of the M * B rows (``idx``, the gathered rows and the slab hold the clients' rows back
+//         to back) with client c's weights and image, which lie at the fixed strides cohort_pstride /
+//         kCohortWprepStride from ``params`` / ``wprep``.  Both strides follow from ``nc``, so the argument list is
+//         unchanged, and c is a workgroup id, not a division.  ``inv_B`` is 1 / B of one client.
+__host__ __device__ constexpr int cohort_pstride(int P) { return (P + 63) / 64 * 64; }  // floats between clients
+constexpr int kCohortWprepStride = (WP_BYTES + 127) / 128 * 128;                          // bytes between images
+
 template <int WAVES, int MODE, bool F32, bool PF, bool PK = false>
 __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     const float* __restrict__ X, long ldx,               // dataset windows [N, ldx]
@@ -983,9 +991,15 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   TinySample<WAVES, F32, PF, PK> S(smem, L, nc);
   constexpr bool TRAIN = MODE != 1;
+  constexpr bool COHORT = MODE == 3;
   const int tid = threadIdx.x;
-  const int b = blockIdx.x;
-  const __amdgpu_buffer_rsrc_t slab_r = make_rsrc(out, (long)gridDim.x * out_stride * 4);
+  const int b = COHORT ? blockIdx.y * gridDim.x + blockIdx.x : blockIdx.x;
+  const long rows = COHORT ? (long)gridDim.x * gridDim.y : (long)gridDim.x;
+  if constexpr (COHORT) {
+    params += (long)blockIdx.y * cohort_pstride(S.lay.P);
+    if constexpr (PF) wprep += (long)blockIdx.y * kCohortWprepStride;
+  }
+  const __amdgpu_buffer_rsrc_t slab_r = make_rsrc(out, rows * out_stride * 4);
   const int rowbase = b * out_stride;
   if (stamps && tid == 0) stamps[(long)b * 16 + 15] = __builtin_amdgcn_s_memrealtime();
 #pragma unroll 1
@@ -1386,6 +1400,102 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_dp_sgd_kernel
   }
 }
 
+// ---------------------------------------------------------------------------- cohorts of virtual clients
+// A cohort round trains M stateless virtual clients of B windows each side by side: one step launch of M * B
+// workgroups and one reduce launch of M x the plain reduce's blocks per step, between a fan-out of the global weights
+// and the mean of the clients' weights.  Client c's weights / momentum are at ``params`` / ``mom`` + c * pstride
+// floats (cohort_pstride), its image at ``wprep`` + c * kCohortWprepStride bytes, its loss word at loss_acc[c] and its
+// slab rows at [c * B, (c + 1) * B).  The step kernel is tiny_ecg_step_kernel's MODE 3.  (Templates, like the DP
+// kernels: emitted after every older kernel.)
+// ``slab_reduce_sgd_kernel`` for M clients in one launch: block c * nblk + j (nblk = the plain reduce's block count)
+// is the plain kernel's block j on client c's G slab rows, weights, momentum, image and loss word - the same
+// column-to-block map, row chunking, summation order and epilogue, so with M == 1 the results are the plain
+// kernel's bits.  Blocks >= nred = M * nblk gather the next step's M * G rows (ga.B).  Same argument order.
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_sgd_kernel(
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
+    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, GatherArgs ga) {
+  constexpr int NT = RED_COLS * RED_ROWG;
+  const int nesterov = flags & kRedNesterov;
+  if ((int)blockIdx.x >= nred) {  // block-uniform: gather blocks never reach the barrier below
+    gather_block<NT>(ga, nred);
+    return;
+  }
+  const int nblk = (P + RED_COLS) / RED_COLS;  // blocks per client: columns 0 .. P
+  const int client = (int)blockIdx.x / nblk;
+  const int pstride = cohort_pstride(P);
+  slab += (long)client * G * stride;
+  params += (long)client * pstride;
+  mom += (long)client * pstride;  // (only dereferenced when momentum != 0, which needs a momentum buffer)
+  if (wprep) wprep += (long)client * kCohortWprepStride;
+  __shared__ float part[RED_ROWG][RED_COLS + 1];
+  const int cl = threadIdx.x % RED_COLS, rg = threadIdx.x / RED_COLS;
+  const int col = ((int)blockIdx.x - client * nblk) * RED_COLS + cl;
+  const bool upd = rg == 0 && col < P;
+  const float p0 = upd ? params[col] : 0.f;
+  const float m0 = (upd && momentum != 0.f) ? mom[col] : 0.f;
+  float s = 0.f;
+  if (col <= P) {
+    const float* base = slab + col;
+    int r = rg;
+    for (; r + RED_ROWG * 15 < G; r += RED_ROWG * 16) {
+      float v[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = base[(long)(r + RED_ROWG * j) * stride];
+#pragma unroll
+      for (int j = 0; j < 16; j += 2) s += v[j] + v[j + 1];
+    }
+    for (; r < G; r += RED_ROWG) s += base[(long)r * stride];
+  }
+  part[rg][cl] = s;
+  __syncthreads();
+  if (rg == 0 && col <= P) {
+    float gsum = 0.f;
+#pragma unroll
+    for (int j = 0; j < RED_ROWG; ++j) gsum += part[j][cl];
+    if (col == P) {
+      if (loss_acc) loss_acc[client] += gsum;
+    } else {
+      const float p = p0;
+      float d = gsum + wd * p;
+      if (momentum != 0.f) {
+        const float bm = momentum * m0 + d;
+        mom[col] = bm;
+        d = nesterov ? d + momentum * bm : bm;
+      }
+      const float pn = p - lr * d;
+      params[col] = pn;
+      if (wprep) wprep_put(wprep, col, pn);
+    }
+  }
+}
+
+// Start of a cohort round: every client's weights = the global weights, every momentum = 0 (virtual clients keep no
+// state between rounds).  grid (ceil(P / NT), M); the pstride - P padding floats of a client are not written.
+template <int NT>
+__global__ __launch_bounds__(NT) void cohort_fanout_kernel(const float* __restrict__ global_params,
+                                                           float* __restrict__ params, float* __restrict__ mom, int P) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= P) return;
+  const long o = (long)blockIdx.y * cohort_pstride(P) + i;
+  params[o] = global_params[i];
+  if (mom) mom[o] = 0.f;
+}
+
+// End of a cohort round: global[i] = (((p_0[i] + p_1[i]) + ...) + p_{M-1}[i]) * inv_M in fp32, clients in ascending
+// order (inv_M = 1.0f / M, rounded once on the host): one fixed order, so the mean is reproducible.
+template <int NT>
+__global__ __launch_bounds__(NT) void cohort_mean_kernel(const float* __restrict__ params,
+                                                         float* __restrict__ global_params, int P, int M, float inv_M) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= P) return;
+  const int pstride = cohort_pstride(P);
+  float s = params[i];
+  for (int c = 1; c < M; ++c) s += params[(long)c * pstride + i];
+  global_params[i] = s * inv_M;
+}
+
 unsigned long long* g_stamps = nullptr;  // diagnostic phase stamps (ecg_tiny_set_stamps)
 
 FusedOpt no_fuse() {
@@ -1748,29 +1858,20 @@ static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
   return ecg::kOk;
 }
 
-// The round's kernels enqueued on ``stream``, without a graph.
-ECG_API int ecg_tiny_round_enqueue(const EcgTinyRound* round, hipStream_t stream) {
-  const int st = check_round(round);
-  return st ? st : enqueue_round(*round, stream);
-}
-
-// The same launches captured into one hipGraph (replayed by ecg_round_graph_launch).  All pointers are baked
-// into the graph: callers keep the buffers alive and refill ``idx`` in place.
-ECG_API int ecg_tiny_round_capture(void** handle, const EcgTinyRound* round) {
-  if (!handle) return ecg::kBadArg;
-  int st = check_round(round);
-  if (st) return st;
+// ``enqueue(stream)``'s launches captured into one instantiated hipGraph (the handle of ecg_round_graph_*).
+template <class Enqueue>
+static int capture_round(void** handle, int steps, Enqueue enqueue) {
   hipStream_t cap;
   ECG_HIP_CHECK(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
   RoundGraph* rg = new RoundGraph();
-  rg->steps = round->steps;
+  rg->steps = steps;
   hipError_t e = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) {
     delete rg;
     (void)hipStreamDestroy(cap);
     return ecg::kHipError;
   }
-  st = enqueue_round(*round, cap);
+  const int st = enqueue(cap);
   e = hipStreamEndCapture(cap, &rg->graph);
   (void)hipStreamDestroy(cap);
   if (st != 0 || e != hipSuccess) {
@@ -1786,6 +1887,21 @@ ECG_API int ecg_tiny_round_capture(void** handle, const EcgTinyRound* round) {
   }
   *handle = rg;
   return ecg::kOk;
+}
+
+// The round's kernels enqueued on ``stream``, without a graph.
+ECG_API int ecg_tiny_round_enqueue(const EcgTinyRound* round, hipStream_t stream) {
+  const int st = check_round(round);
+  return st ? st : enqueue_round(*round, stream);
+}
+
+// The same launches captured into one hipGraph (replayed by ecg_round_graph_launch).  All pointers are baked
+// into the graph: callers keep the buffers alive and refill ``idx`` in place.
+ECG_API int ecg_tiny_round_capture(void** handle, const EcgTinyRound* round) {
+  if (!handle) return ecg::kBadArg;
+  const int st = check_round(round);
+  if (st) return st;
+  return capture_round(handle, round->steps, [&](hipStream_t cap) { return enqueue_round(*round, cap); });
 }
 
 // Floats of the gather buffer ``xg`` of a round (its ``yg`` holds 2 * B int32).
@@ -1817,4 +1933,165 @@ ECG_API int ecg_round_graph_destroy(void* handle) {
   if (rg->graph) (void)hipGraphDestroy(rg->graph);
   delete rg;
   return ecg::kOk;
+}
+
+// ---------------------------------------------------------------------------- cohort rounds
+// Floats between two clients' weights (and momenta) in a cohort's ``params`` / ``mom``: >= P, a multiple of 64.
+ECG_API int ecg_tiny_cohort_param_stride(int nc) { return cohort_pstride(make_layout(nc).P); }
+
+// Bytes between two clients' prepared-fragment images in a cohort's ``wprep``: >= ecg_tiny_wprep_bytes(), 16 | it.
+ECG_API int ecg_tiny_cohort_wprep_stride(void) { return kCohortWprepStride; }
+
+// A cohort round: M virtual clients of B windows each start from ``global_params`` (fanout), run ``steps`` local SGD
+// steps side by side - one step launch and one reduce launch per step for the whole cohort - and their weights' mean
+// (ascending client order, cohort_mean_kernel) becomes ``global_params``.  Client c: weights / momentum at
+// ``params`` / ``mom`` + c * ecg_tiny_cohort_param_stride(nc) floats, image at ``wprep`` + c *
+// ecg_tiny_cohort_wprep_stride() bytes (zero-initialised by the caller, like a single client's), loss word
+// loss_acc[c], slab rows [c * B, (c + 1) * B), columns [c * B, (c + 1) * B) of every ``idx`` row.  bf16 rounds run
+// like a packed EcgTinyRound - the first step builds its operands in LDS, later steps read the images and the packed
+// rows gathered by the previous reduce - and need wprep, xg, yg and xbg, sized for M * B rows
+// (ecg_tiny_gather_floats / _halfs(L, M * B)); fp32 rounds take none of them.  There is no DP-SGD in a cohort.
+// ops/_lib.py mirrors this struct (TinyCohortRound) and checks its size against ecg_tiny_cohort_round_sizeof().
+struct EcgTinyCohortRound {
+  const float* X;
+  long ldx;
+  const int* idx;  // [steps][M * B] batch rows, read in place
+  const int* Y;
+  float* params;         // [M][pstride] client weights (scratch between rounds unless fanout == 0)
+  float* mom;            // [M][pstride] (may be null when momentum == 0)
+  float* slab;           // [M * B][slab_stride]
+  float* loss_acc;       // [M] += each client's summed sample losses (nullable)
+  void* wprep;           // [M] images at the wprep stride (bf16)
+  float* xg;             // [2][M * B][ldg] (bf16)
+  int* yg;               // [2][M * B] (bf16)
+  void* xbg;             // bf16 [2][M * B][ldb] (bf16)
+  float* global_params;  // [P]: read by the fan-out, written by the mean
+  int L, nc, slab_stride, B, steps, M;
+  int fanout;  // 0: the clients start from what ``params`` / ``mom`` hold (tests: distinct weights per client)
+  float lr, momentum, wd;
+  int nesterov, prec;
+};
+
+ECG_API int ecg_tiny_cohort_round_sizeof(void) { return (int)sizeof(EcgTinyCohortRound); }
+
+namespace {
+
+// (The cohort kernels are first named here, behind every older launch site, so that they are instantiated last.)
+// One cohort step launch (MODE 3): grid (a.B, M), ``a.params`` / ``a.wprep`` client 0's, ``a.out`` the M * a.B-row slab.
+template <int WAVES, bool F32, bool PF, bool PK = false>
+int launch_cohort_step(const StepArgs& a, int M, hipStream_t stream) {
+  const Smem sm = make_smem(a.L, WAVES, a.nc, F32);
+  auto kern = tiny_ecg_step_kernel<WAVES, 3, F32, PF, PK>;
+  if (sm.bytes > 64 * 1024)
+    ECG_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, sm.bytes));
+  if (PK && a.idx) return ecg::kBadArg;  // the PK kernel reads row b
+  hipLaunchKernelGGL(kern, dim3(a.B, M), dim3(WAVES * 64), sm.bytes, stream, a.X, a.ldx, PF ? a.wprep : nullptr, a.Y,
+                     g_stamps, a.L, a.nc, a.params, a.out, a.out_stride, a.inv_B, a.idx, no_fuse().slab_wt);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+// The cohort forms of the three kernels a production round launches: fp32; bf16 building its operands in LDS (a
+// round's first step: ``a.wprep`` null); bf16 on packed rows and the images (``a.packed``).  Arguments are checked
+// by check_cohort_round.
+int cohort_step_dispatch(int prec, const StepArgs& a, int M, hipStream_t stream) {
+  const bool w8 = pick_waves(a.L, prec == 1) == 8;
+  if (prec == 1) return w8 ? launch_cohort_step<8, true, false>(a, M, stream) : launch_cohort_step<16, true, false>(a, M, stream);
+  if (a.packed)
+    return w8 ? launch_cohort_step<8, false, true, true>(a, M, stream)
+              : launch_cohort_step<16, false, true, true>(a, M, stream);
+  if (a.wprep) return ecg::kBadArg;  // the unpacked prepared-fragment kernel has no cohort form
+  return w8 ? launch_cohort_step<8, false, false>(a, M, stream) : launch_cohort_step<16, false, false>(a, M, stream);
+}
+
+// The cohort reduce + SGD of one step: M x the plain reduce's blocks, then the gather blocks of the next step.
+int cohort_reduce_dispatch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
+                           float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
+                           hipStream_t stream, const GatherArgs* gather = nullptr) {
+  constexpr int cols = kRedColsDefault;
+  const int nred = M * ((P + cols) / cols);
+  GatherArgs ga{};
+  int grid = nred;
+  if (gather) {
+    ga = *gather;
+    const int rpb = gather_rows_per_block(ga.L, ga.vec, cols * RED_ROWG);
+    grid += (ga.B + rpb - 1) / rpb;
+  }
+  hipLaunchKernelGGL(slab_reduce_cohort_sgd_kernel<cols>, dim3(grid), dim3(cols * RED_ROWG), 0, stream, slab, params,
+                     mom, nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc, ga);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+}  // namespace
+
+static int check_cohort_round(const EcgTinyCohortRound* r) {
+  if (!r || r->steps < 1 || r->M < 1 || r->M > 65535) return ecg::kBadArg;  // (M is the grid's y extent)
+  if (!r->X || !r->Y || !r->idx || !r->params || !r->slab || !r->global_params) return ecg::kBadArg;
+  if (r->momentum != 0.f && !r->mom) return ecg::kBadArg;
+  if (r->prec != 0 && r->prec != 1) return ecg::kBadArg;
+  const bool gath = r->wprep && r->xg && r->yg && r->xbg, none = !r->wprep && !r->xg && !r->yg && !r->xbg;
+  if (r->prec == 0 ? !gath : !none) return ecg::kBadArg;
+  const int st = check_step_args(r->L, r->nc, r->B, r->slab_stride, 0, r->prec == 1);
+  if (st) return st;
+  // the slab and gather buffer resources hold byte sizes in 32 bits, and their row offsets are ints
+  const long rows = (long)r->M * r->B;
+  if (rows * r->slab_stride * 4 > INT_MAX || rows * (pack_ldb(r->L) + 8) * 4 > INT_MAX) return ecg::kTooLarge;
+  return ecg::kOk;
+}
+
+static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream) {
+  const int P = make_layout(r.nc).P, rows = r.M * r.B;
+  unsigned char* wprep = static_cast<unsigned char*>(r.wprep);
+  const int ldg = (r.L + 3) / 4 * 4, ldb = pack_ldb(r.L);
+  __bf16* xbg = static_cast<__bf16*>(r.xbg);
+  const bool bf16 = r.prec == 0;
+  if (r.fanout) {
+    hipLaunchKernelGGL(cohort_fanout_kernel<256>, dim3((P + 255) / 256, r.M), dim3(256), 0, stream, r.global_params,
+                       r.params, r.mom, P);
+    ECG_HIP_CHECK(hipGetLastError());
+  }
+  GatherArgs ga{r.X, r.ldx, nullptr, r.Y, nullptr, nullptr, r.L, ldg, rows,
+                (r.L % 4 == 0 && r.ldx % 4 == 0 && reinterpret_cast<uintptr_t>(r.X) % 16 == 0) ? 1 : 0, nullptr, ldb};
+  for (int s = 0; s < r.steps; ++s) {
+    const int* idx = r.idx + (long)s * rows;
+    const bool gather_next = bf16 && s + 1 < r.steps;
+    if (gather_next) {  // ping-pong buffers as in enqueue_round, M * B rows each
+      ga.idx = idx + rows;
+      ga.xg = r.xg + (long)((s + 1) & 1) * rows * ldg;
+      ga.yg = r.yg + (long)((s + 1) & 1) * rows;
+      ga.xbg = xbg + (long)((s + 1) & 1) * rows * ldb;
+    }
+    StepArgs a{r.X, r.L, r.ldx, idx, r.Y, r.params, r.nc, r.slab, r.slab_stride, r.B, 1.0f / (float)r.B, nullptr};
+    if (bf16 && s > 0) {
+      a.X = reinterpret_cast<const float*>(xbg + (long)(s & 1) * rows * ldb);
+      a.ldx = ldb / 2;
+      a.idx = nullptr;
+      a.Y = r.yg + (long)(s & 1) * rows;
+      a.wprep = wprep;
+      a.packed = true;
+    }
+    int st = cohort_step_dispatch(r.prec, a, r.M, stream);
+    if (st) return st;
+    st = cohort_reduce_dispatch(r.slab, r.B, r.M, r.slab_stride, P, r.params, r.mom, r.loss_acc, r.lr, r.momentum, r.wd,
+                                r.nesterov, wprep, stream, gather_next ? &ga : nullptr);
+    if (st) return st;
+  }
+  hipLaunchKernelGGL(cohort_mean_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, r.params, r.global_params,
+                     P, r.M, 1.0f / (float)r.M);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+ECG_API int ecg_tiny_cohort_round_enqueue(const EcgTinyCohortRound* round, hipStream_t stream) {
+  const int st = check_cohort_round(round);
+  return st ? st : enqueue_cohort_round(*round, stream);
+}
+
+// The cohort round as one hipGraph; the handle is the one ecg_round_graph_launch / _upload / _destroy take.
+ECG_API int ecg_tiny_cohort_round_capture(void** handle, const EcgTinyCohortRound* round) {
+  if (!handle) return ecg::kBadArg;
+  const int st = check_cohort_round(round);
+  if (st) return st;
+  return capture_round(handle, round->steps, [&](hipStream_t cap) { return enqueue_cohort_round(*round, cap); });
 }

@@ -13,6 +13,8 @@ New flags: --kernel-backend {auto,fused,torch} --amp-dtype {bf16,fp16,none} --ov
 each client's held-out last H windows)
 --dp-clip C --dp-noise sigma --dp-delta delta --privacy-csv path (DP-SGD local steps: per-sample clip + Gaussian
 noise; cumulative epsilon per round, Poisson-subsampling bound; the reported training loss is not private)
+--clients-per-gpu K --cohort M --cohort-csv path (client sampling: K virtual clients per GPU, M of them drawn per
+round and trained side by side from the global weights; TinyECG on the fused or torch backend)
 """
 from __future__ import annotations
 
