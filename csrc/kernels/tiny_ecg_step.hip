@@ -1124,8 +1124,7 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
 // instruction), G, stride, P, the apply / nesterov flags (one dword) and momentum (dwords 6-11) - and the two scalars
 // of the update, lr and wd (12-13), so that the epilogue behind the barrier starts no scalar load of its own.  The
 // image, loss and gradient-copy pointers are fetched under the slab loads; the gather blocks' GatherArgs, about 80
-// bytes by value, comes last - nothing waits for those blocks.  slab_reduce_dp_sgd_kernel keeps the same order and
-// appends its own arguments.
+// bytes by value, comes last - nothing waits for those blocks.  The DP and cohort kernels keep this order.
 constexpr int kRedColsDefault = 32;
 constexpr int kRedApply = 1, kRedNesterov = 2;
 inline int red_flags(int apply, int nesterov) { return (apply ? kRedApply : 0) | (nesterov ? kRedNesterov : 0); }
@@ -1193,40 +1192,67 @@ __device__ __forceinline__ void gather_block(const GatherArgs& ga, int nred) {
 }
 static_assert(kPackLead == 4, "gather_block's 4-float form writes the lead as one 8-byte unit");
 
-template <int RED_COLS>
-__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_sgd_kernel(
-    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom,
-    int nred,   // blocks below this index reduce, the rest gather; INT_MAX = no gather
-    int G, int stride, int P,
-    int flags,  // kRedApply | kRedNesterov
-    float momentum, float lr, float wd,  // -- preloaded up to here
-    unsigned char* __restrict__ wprep,   // PF image kept current with the updated parameters (nullable)
-    float* __restrict__ loss_acc, float* __restrict__ grad_out, GatherArgs ga) {
+// defined with the DP kernels
+__device__ inline float dp_normal(int i, unsigned long long seed, unsigned long long t);
+
+// The one body of the three reduce kernels.  DP: every loaded gradient value is multiplied by its row's clip factor
+// ``scale[row]`` and ``noise_scale`` * z_col is added to the column sum before the epilogue (the loss column is neither
+// scaled nor noised; noise_scale == 0: no noise is drawn).  COHORT: block c * nblk + j (nblk = the single-client block
+// count) is block j on client c's G slab rows, weights, momentum, image and loss word; the update is always applied.
+// Column-to-block map, row chunking, summation order and epilogue are these lines for all three, so DP with every
+// scale[b] == 1 and no noise, and a cohort of one, give the plain kernel's bits.  The pointers carry no __restrict__
+// here: the kernels' own parameters do, and a second set of alias scopes from the inlined body changes the gather
+// branch's code (profiles/r12/tiny_reduce_merge.txt).
+template <int RED_COLS, bool DP, bool COHORT>
+__device__ __forceinline__ void slab_reduce_body(
+    const float* slab, float* params, float* mom, int nred, int G, int stride, int P, int flags, float momentum,
+    float lr, float wd, unsigned char* wprep, float* loss_acc, float* grad_out, const float* scale, float noise_scale,
+    unsigned long long seed, const unsigned long long* dp_step, const GatherArgs& ga) {
   constexpr int NT = RED_COLS * RED_ROWG;
-  const int apply = flags & kRedApply, nesterov = flags & kRedNesterov;
+  const int apply = COHORT ? 1 : flags & kRedApply, nesterov = flags & kRedNesterov;
   if ((int)blockIdx.x >= nred) {  // block-uniform: gather blocks never reach the barrier below
     gather_block<NT>(ga, nred);
     return;
   }
+  int blk = blockIdx.x, client = 0;
+  if constexpr (COHORT) {
+    const int nblk = (P + RED_COLS) / RED_COLS;  // blocks per client: columns 0 .. P
+    client = blk / nblk;
+    const int pstride = cohort_pstride(P);
+    slab += (long)client * G * stride;
+    params += (long)client * pstride;
+    mom += (long)client * pstride;  // (only dereferenced when momentum != 0, which needs a momentum buffer)
+    if (wprep) wprep += (long)client * kCohortWprepStride;
+    blk -= client * nblk;
+  }
   __shared__ float part[RED_ROWG][RED_COLS + 1];
   const int cl = threadIdx.x % RED_COLS, rg = threadIdx.x / RED_COLS;
-  const int col = blockIdx.x * RED_COLS + cl;
+  const int col = blk * RED_COLS + cl;
   // the updating threads fetch their parameter / momentum before the slab reads: one round trip, not two
   const bool upd = rg == 0 && col < P && apply;
   const float p0 = upd ? params[col] : 0.f;
   const float m0 = (upd && momentum != 0.f) ? mom[col] : 0.f;
+  float noise = 0.f;  // drawn before the slab reads, under their latency
+  if constexpr (DP)
+    if (rg == 0 && col < P && noise_scale != 0.f) noise = noise_scale * dp_normal(col, seed, dp_step[0] - 1ull);
   float s = 0.f;
   if (col <= P) {
     const float* base = slab + col;
+    const bool grad_col = col < P;  // DP: the loss column is summed as it is
+    auto load = [&](int rr) {
+      const float v = base[(long)rr * stride];
+      if constexpr (DP) return v * (grad_col ? scale[rr] : 1.f);
+      else return v;
+    };
     int r = rg;
     for (; r + RED_ROWG * 15 < G; r += RED_ROWG * 16) {
       float v[16];
 #pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = base[(long)(r + RED_ROWG * j) * stride];
+      for (int j = 0; j < 16; ++j) v[j] = load(r + RED_ROWG * j);
 #pragma unroll
       for (int j = 0; j < 16; j += 2) s += v[j] + v[j + 1];
     }
-    for (; r < G; r += RED_ROWG) s += base[(long)r * stride];
+    for (; r < G; r += RED_ROWG) s += load(r);
   }
   part[rg][cl] = s;
   __syncthreads();
@@ -1235,8 +1261,10 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_sgd_kernel(
 #pragma unroll
     for (int j = 0; j < RED_ROWG; ++j) gsum += part[j][cl];
     if (col == P) {
-      if (loss_acc) loss_acc[0] += gsum;
+      if (loss_acc) loss_acc[client] += gsum;
     } else {
+      if constexpr (DP)
+        if (noise_scale != 0.f) gsum += noise;
       if (grad_out) grad_out[col] = gsum;
       if (apply) {
         const float p = p0;
@@ -1254,9 +1282,22 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_sgd_kernel(
   }
 }
 
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_sgd_kernel(
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom,
+    int nred,   // blocks below this index reduce, the rest gather; INT_MAX = no gather
+    int G, int stride, int P,
+    int flags,  // kRedApply | kRedNesterov
+    float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep,   // PF image kept current with the updated parameters (nullable)
+    float* __restrict__ loss_acc, float* __restrict__ grad_out, GatherArgs ga) {
+  slab_reduce_body<RED_COLS, false, false>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
+                                           loss_acc, grad_out, nullptr, 0.f, 0ull, nullptr, ga);
+}
+
 // ---------------------------------------------------------------------------- DP-SGD (per-sample clip + noise)
 // The slab already holds one gradient row per sample, so DP-SGD only changes the reduce side: a row-norm launch
-// writes the clip factors c_b = min(1, C / n_b) and ``slab_reduce_sgd_kernel``'s twin sums c_b * row_b, adds
+// writes the clip factors c_b = min(1, C / n_b) and ``slab_reduce_dp_sgd_kernel`` sums c_b * row_b, adds
 // sigma * C / B * z_i and runs the same SGD / wprep / gather epilogue.  The step kernel is not involved.
 //
 // Noise is counter-based so that a graph replay, an enqueued round and the torch backend (utils/philox.py) draw the
@@ -1331,10 +1372,8 @@ __global__ __launch_bounds__(ROWS * 64) void dp_row_scale_kernel(
   }
 }
 
-// ``slab_reduce_sgd_kernel`` with every loaded gradient value multiplied by its row's clip factor and
-// ``noise_scale`` * z_col added to the column sum before the epilogue (noise_scale = sigma * C / B; 0: no noise is
-// drawn).  Same column-to-block map, row chunking and summation order: with every scale[b] == 1 and noise_scale == 0
-// the results are bitwise the plain kernel's.  The loss column is neither scaled nor noised.
+// slab_reduce_body's DP form: ``scale`` [G] from dp_row_scale_kernel, noise_scale = sigma * C / B.  The plain
+// kernel's argument order with the DP arguments in front of ``ga``.
 template <int RED_COLS>
 __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_dp_sgd_kernel(
     const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
@@ -1342,62 +1381,8 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_dp_sgd_kernel
     unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, float* __restrict__ grad_out,
     const float* __restrict__ scale, float noise_scale, unsigned long long seed,
     const unsigned long long* __restrict__ dp_step, GatherArgs ga) {
-  constexpr int NT = RED_COLS * RED_ROWG;
-  const int apply = flags & kRedApply, nesterov = flags & kRedNesterov;
-  if ((int)blockIdx.x >= nred) {  // block-uniform: gather blocks never reach the barrier below
-    gather_block<NT>(ga, nred);
-    return;
-  }
-  __shared__ float part[RED_ROWG][RED_COLS + 1];
-  const int cl = threadIdx.x % RED_COLS, rg = threadIdx.x / RED_COLS;
-  const int col = blockIdx.x * RED_COLS + cl;
-  const bool upd = rg == 0 && col < P && apply;
-  const float p0 = upd ? params[col] : 0.f;
-  const float m0 = (upd && momentum != 0.f) ? mom[col] : 0.f;
-  float noise = 0.f;  // drawn before the slab reads, under their latency
-  if (rg == 0 && col < P && noise_scale != 0.f) noise = noise_scale * dp_normal(col, seed, dp_step[0] - 1ull);
-  float s = 0.f;
-  if (col <= P) {
-    const float* base = slab + col;
-    const bool grad_col = col < P;  // the loss column is summed as it is
-    int r = rg;
-    for (; r + RED_ROWG * 15 < G; r += RED_ROWG * 16) {
-      float v[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int rr = r + RED_ROWG * j;
-        v[j] = base[(long)rr * stride] * (grad_col ? scale[rr] : 1.f);
-      }
-#pragma unroll
-      for (int j = 0; j < 16; j += 2) s += v[j] + v[j + 1];
-    }
-    for (; r < G; r += RED_ROWG) s += base[(long)r * stride] * (grad_col ? scale[r] : 1.f);
-  }
-  part[rg][cl] = s;
-  __syncthreads();
-  if (rg == 0 && col <= P) {
-    float gsum = 0.f;
-#pragma unroll
-    for (int j = 0; j < RED_ROWG; ++j) gsum += part[j][cl];
-    if (col == P) {
-      if (loss_acc) loss_acc[0] += gsum;
-    } else {
-      if (noise_scale != 0.f) gsum += noise;
-      if (grad_out) grad_out[col] = gsum;
-      if (apply) {
-        const float p = p0;
-        float d = gsum + wd * p;
-        if (momentum != 0.f) {
-          const float bm = momentum * m0 + d;
-          mom[col] = bm;
-          d = nesterov ? d + momentum * bm : bm;
-        }
-        const float pn = p - lr * d;
-        params[col] = pn;
-        if (wprep) wprep_put(wprep, col, pn);
-      }
-    }
-  }
+  slab_reduce_body<RED_COLS, true, false>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
+                                          loss_acc, grad_out, scale, noise_scale, seed, dp_step, ga);
 }
 
 // ---------------------------------------------------------------------------- cohorts of virtual clients
@@ -1407,68 +1392,15 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_dp_sgd_kernel
 // floats (cohort_pstride), its image at ``wprep`` + c * kCohortWprepStride bytes, its loss word at loss_acc[c] and its
 // slab rows at [c * B, (c + 1) * B).  The step kernel is tiny_ecg_step_kernel's MODE 3.  (Templates, like the DP
 // kernels: emitted after every older kernel.)
-// ``slab_reduce_sgd_kernel`` for M clients in one launch: block c * nblk + j (nblk = the plain reduce's block count)
-// is the plain kernel's block j on client c's G slab rows, weights, momentum, image and loss word - the same
-// column-to-block map, row chunking, summation order and epilogue, so with M == 1 the results are the plain
-// kernel's bits.  Blocks >= nred = M * nblk gather the next step's M * G rows (ga.B).  Same argument order.
+// slab_reduce_body's COHORT form, M clients in one launch: blocks >= nred = M * nblk gather the next step's M * G rows
+// (ga.B).  The plain kernel's argument order without ``grad_out``; the apply flag is not read.
 template <int RED_COLS>
 __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_sgd_kernel(
     const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
     int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
     unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, GatherArgs ga) {
-  constexpr int NT = RED_COLS * RED_ROWG;
-  const int nesterov = flags & kRedNesterov;
-  if ((int)blockIdx.x >= nred) {  // block-uniform: gather blocks never reach the barrier below
-    gather_block<NT>(ga, nred);
-    return;
-  }
-  const int nblk = (P + RED_COLS) / RED_COLS;  // blocks per client: columns 0 .. P
-  const int client = (int)blockIdx.x / nblk;
-  const int pstride = cohort_pstride(P);
-  slab += (long)client * G * stride;
-  params += (long)client * pstride;
-  mom += (long)client * pstride;  // (only dereferenced when momentum != 0, which needs a momentum buffer)
-  if (wprep) wprep += (long)client * kCohortWprepStride;
-  __shared__ float part[RED_ROWG][RED_COLS + 1];
-  const int cl = threadIdx.x % RED_COLS, rg = threadIdx.x / RED_COLS;
-  const int col = ((int)blockIdx.x - client * nblk) * RED_COLS + cl;
-  const bool upd = rg == 0 && col < P;
-  const float p0 = upd ? params[col] : 0.f;
-  const float m0 = (upd && momentum != 0.f) ? mom[col] : 0.f;
-  float s = 0.f;
-  if (col <= P) {
-    const float* base = slab + col;
-    int r = rg;
-    for (; r + RED_ROWG * 15 < G; r += RED_ROWG * 16) {
-      float v[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = base[(long)(r + RED_ROWG * j) * stride];
-#pragma unroll
-      for (int j = 0; j < 16; j += 2) s += v[j] + v[j + 1];
-    }
-    for (; r < G; r += RED_ROWG) s += base[(long)r * stride];
-  }
-  part[rg][cl] = s;
-  __syncthreads();
-  if (rg == 0 && col <= P) {
-    float gsum = 0.f;
-#pragma unroll
-    for (int j = 0; j < RED_ROWG; ++j) gsum += part[j][cl];
-    if (col == P) {
-      if (loss_acc) loss_acc[client] += gsum;
-    } else {
-      const float p = p0;
-      float d = gsum + wd * p;
-      if (momentum != 0.f) {
-        const float bm = momentum * m0 + d;
-        mom[col] = bm;
-        d = nesterov ? d + momentum * bm : bm;
-      }
-      const float pn = p - lr * d;
-      params[col] = pn;
-      if (wprep) wprep_put(wprep, col, pn);
-    }
-  }
+  slab_reduce_body<RED_COLS, false, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
+                                          loss_acc, nullptr, nullptr, 0.f, 0ull, nullptr, ga);
 }
 
 // Start of a cohort round: every client's weights = the global weights, every momentum = 0 (virtual clients keep no
@@ -1523,14 +1455,15 @@ struct StepArgs {
   bool packed = false;  // X holds packed bf16 rows (PK kernel: MODE 0, bf16, wprep; idx == nullptr)
 };
 
+// MODE 3 (cohort): grid (a.B, M), ``a.params`` / ``a.wprep`` client 0's, ``a.out`` the M * a.B-row slab.
 template <int WAVES, int MODE, bool F32, bool PF, bool PK = false>
-int launch_step(const StepArgs& a, hipStream_t stream) {
+int launch_step(const StepArgs& a, hipStream_t stream, int M = 1) {
   const Smem sm = make_smem(a.L, WAVES, a.nc, F32);
   auto kern = tiny_ecg_step_kernel<WAVES, MODE, F32, PF, PK>;
   if (sm.bytes > 64 * 1024)
     ECG_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, sm.bytes));
   if (PK && a.idx) return ecg::kBadArg;  // the PK kernel reads row b
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(WAVES * 64), sm.bytes, stream, a.X, a.ldx, PF ? a.wprep : nullptr, a.Y,
+  hipLaunchKernelGGL(kern, dim3(a.B, M), dim3(WAVES * 64), sm.bytes, stream, a.X, a.ldx, PF ? a.wprep : nullptr, a.Y,
                      g_stamps, a.L, a.nc, a.params, a.out, a.out_stride, a.inv_B, a.idx, no_fuse().slab_wt);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
@@ -1599,23 +1532,43 @@ int step_dispatch(int mode, int prec, const StepArgs& a, hipStream_t stream) {
   return dispatch_cfg<false, false>(mode, waves, a, stream);
 }
 
+// The argument checks every reduce launch shares.
+int check_reduce(int G, int stride, int P, int apply, const float* params, float momentum, const float* mom) {
+  if (G <= 0 || P <= 0 || stride < P + 1) return ecg::kBadArg;
+  if (apply && (!params || (momentum != 0.f && !mom))) return ecg::kBadArg;
+  return ecg::kOk;
+}
+
+// Launch geometry of a reduce over M clients' slabs: ``blocks`` reduce blocks per client (columns 0 .. P,
+// kRedColsDefault per block; A/B: profiles/r1_final/ab_red_cols.txt), then the gather blocks of ``gather`` (nullable,
+// copied into ``ga``).  ``nred`` is the first gather block: M * blocks, or INT_MAX when a single client's reduce has
+// none.
+constexpr int kRedThreads = kRedColsDefault * RED_ROWG;
+struct RedGeom {
+  int blocks, nred, grid;
+  GatherArgs ga;
+};
+RedGeom red_geom(int P, int M, const GatherArgs* gather, bool cohort = false) {
+  RedGeom g{(P + kRedColsDefault) / kRedColsDefault, 0, 0, {}};
+  g.grid = M * g.blocks;
+  g.nred = (gather || cohort) ? g.grid : INT_MAX;
+  if (gather) {
+    g.ga = *gather;
+    const int rpb = gather_rows_per_block(g.ga.L, g.ga.vec, kRedThreads);
+    g.grid += (g.ga.B + rpb - 1) / rpb;
+  }
+  return g;
+}
+
 int reduce_dispatch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
                     float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
                     unsigned char* wprep, hipStream_t stream, const GatherArgs* gather = nullptr) {
-  if (G <= 0 || P <= 0 || stride < P + 1) return ecg::kBadArg;
-  if (apply && (!params || (momentum != 0.f && !mom))) return ecg::kBadArg;
-  constexpr int cols = kRedColsDefault;  // columns per reduction block (A/B: profiles/r1_final/ab_red_cols.txt)
-  const int blocks = (P + 1 + cols - 1) / cols;
-  GatherArgs ga{};
-  int grid = blocks, nred = INT_MAX;
-  if (gather) {
-    ga = *gather;
-    nred = blocks;
-    const int rpb = gather_rows_per_block(ga.L, ga.vec, cols * RED_ROWG);
-    grid += (ga.B + rpb - 1) / rpb;
-  }
-  hipLaunchKernelGGL(slab_reduce_sgd_kernel<cols>, dim3(grid), dim3(cols * RED_ROWG), 0, stream, slab, params, mom,
-                     nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc, grad_out, ga);
+  const int st = check_reduce(G, stride, P, apply, params, momentum, mom);
+  if (st) return st;
+  const RedGeom g = red_geom(P, 1, gather);
+  hipLaunchKernelGGL(slab_reduce_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab, params,
+                     mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc, grad_out,
+                     g.ga);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -1636,28 +1589,18 @@ int check_dp(const DpArgs& d) {
 int dp_reduce_dispatch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
                        float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
                        unsigned char* wprep, const DpArgs& dp, hipStream_t stream, const GatherArgs* gather = nullptr) {
-  if (G <= 0 || P <= 0 || stride < P + 1 || !slab) return ecg::kBadArg;
-  if (apply && (!params || (momentum != 0.f && !mom))) return ecg::kBadArg;
-  const int st = check_dp(dp);
+  int st = slab ? check_reduce(G, stride, P, apply, params, momentum, mom) : ecg::kBadArg;
+  if (!st) st = check_dp(dp);
   if (st) return st;
   const int vec = (stride % 4 == 0 && reinterpret_cast<uintptr_t>(slab) % 16 == 0) ? 1 : 0;
   hipLaunchKernelGGL(dp_row_scale_kernel<DP_ROWS_PER_BLOCK>, dim3((G + DP_ROWS_PER_BLOCK - 1) / DP_ROWS_PER_BLOCK),
                      dim3(DP_ROWS_PER_BLOCK * 64), 0, stream, slab, G, stride, P, dp.clip, dp.scale, dp.step, vec);
   ECG_HIP_CHECK(hipGetLastError());
-  constexpr int cols = kRedColsDefault;
-  const int blocks = (P + 1 + cols - 1) / cols;
-  GatherArgs ga{};
-  int grid = blocks, nred = INT_MAX;
-  if (gather) {
-    ga = *gather;
-    nred = blocks;
-    const int rpb = gather_rows_per_block(ga.L, ga.vec, cols * RED_ROWG);
-    grid += (ga.B + rpb - 1) / rpb;
-  }
+  const RedGeom g = red_geom(P, 1, gather);
   const float noise_scale = dp.sigma * dp.clip / (float)G;
-  hipLaunchKernelGGL(slab_reduce_dp_sgd_kernel<cols>, dim3(grid), dim3(cols * RED_ROWG), 0, stream, slab, params, mom,
-                     nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc, grad_out,
-                     dp.scale, noise_scale, dp.seed, dp.step, ga);
+  hipLaunchKernelGGL(slab_reduce_dp_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
+                     params, mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc,
+                     grad_out, dp.scale, noise_scale, dp.seed, dp.step, g.ga);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -1806,44 +1749,58 @@ static int check_round(const EcgTinyRound* r) {
   return check_step_args(r->L, r->nc, r->B, r->slab_stride, 0, r->prec == 1);
 }
 
+// The gather ping-pong of a round whose steps take ``rows`` windows each: xg [2][rows][ldg], yg [2][rows] and
+// (nullable) the packed bf16 rows xbg [2][rows][ldb].  Step s > 0 reads buffer s & 1, which the reduce launch of step
+// s - 1 filled (stream order: that buffer's previous reader, step s - 2's kernel, finished before that reduce
+// started).  With xbg the step reads the packed rows instead of xg (xg is still written: it is the unpacked kernel's
+// input and the record of what was gathered).
+struct GatherBufs {
+  float* xg;
+  int* yg;
+  __bf16* xbg;
+};
+// What every gather launch of the round shares; gather_fill sets the rest.
+static GatherArgs gather_args(const float* X, long ldx, const int* Y, int L, int rows) {
+  const int vec = (L % 4 == 0 && ldx % 4 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0) ? 1 : 0;
+  return {X, ldx, nullptr, Y, nullptr, nullptr, L, (L + 3) / 4 * 4, rows, vec, nullptr, pack_ldb(L)};
+}
+// The reduce launch of step s gathers step s + 1's batch ``idx_next`` into buffer (s + 1) & 1.
+static void gather_fill(GatherArgs& ga, const GatherBufs& g, int s, const int* idx_next) {
+  const long buf = (long)((s + 1) & 1) * ga.B;
+  ga.idx = idx_next;
+  ga.xg = g.xg + buf * ga.ldg;
+  ga.yg = g.yg + buf;
+  ga.xbg = g.xbg ? g.xbg + buf * ga.ldb : nullptr;
+}
+// Step s reads buffer s & 1 by row.
+static void gather_read(StepArgs& a, const GatherArgs& ga, const GatherBufs& g, int s) {
+  const long buf = (long)(s & 1) * ga.B;
+  a.X = g.xg + buf * ga.ldg;
+  a.ldx = ga.ldg;
+  a.idx = nullptr;
+  a.Y = g.yg + buf;
+  if (g.xbg) {
+    a.X = reinterpret_cast<const float*>(g.xbg + buf * ga.ldb);
+    a.ldx = ga.ldb / 2;
+    a.packed = true;
+  }
+}
+
 // Enqueue a checked round on ``stream`` (a capturing stream included): two launches per step, three with DP-SGD.
 // (Warm-up loads of the next step's windows in the step kernel's tail measured neutral - 11.11 vs 11.08 us/step,
 // the windows already sit in the Infinity Cache; profiles/r2/bench_prefetch.txt - and were removed.)
 static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
   const int P = make_layout(r.nc).P;
   unsigned char* wprep = static_cast<unsigned char*>(r.wprep);
-  // Gathered steps (xg/yg): step s > 0 reads ping-pong buffer s & 1, which the reduce launch of step s - 1 filled
-  // (stream order: that buffer's previous reader, step s - 2's kernel, finished before that reduce started).
-  const int ldg = (r.L + 3) / 4 * 4;
-  // Packed steps (xbg): the same gather also leaves the windows as packed bf16 rows, and step s > 0 reads those
-  // instead of xg (xg is still written: it is the unpacked kernel's input and the record of what was gathered).
-  const int ldb = pack_ldb(r.L);
-  __bf16* xbg = static_cast<__bf16*>(r.xbg);
-  GatherArgs ga{r.X, r.ldx, nullptr, r.Y, nullptr, nullptr, r.L, ldg, r.B,
-                (r.L % 4 == 0 && r.ldx % 4 == 0 && reinterpret_cast<uintptr_t>(r.X) % 16 == 0) ? 1 : 0, nullptr, ldb};
+  const GatherBufs bufs{r.xg, r.yg, static_cast<__bf16*>(r.xbg)};
+  GatherArgs ga = gather_args(r.X, r.ldx, r.Y, r.L, r.B);
   for (int s = 0; s < r.steps; ++s) {
     const int* idx = r.idx ? r.idx + (long)s * r.B : nullptr;
-    const bool gathered = r.xg && s > 0;
     const bool gather_next = r.xg && s + 1 < r.steps;
-    if (gather_next) {
-      ga.idx = idx + r.B;
-      ga.xg = r.xg + (long)((s + 1) & 1) * r.B * ldg;
-      ga.yg = r.yg + (long)((s + 1) & 1) * r.B;
-      ga.xbg = xbg ? xbg + (long)((s + 1) & 1) * r.B * ldb : nullptr;
-    }
+    if (gather_next) gather_fill(ga, bufs, s, idx + r.B);
     StepArgs a{r.X, r.L, r.ldx, idx, r.Y, r.params, r.nc, r.slab, r.slab_stride, r.B, 1.0f / (float)r.B,
                s == 0 ? nullptr : wprep};
-    if (gathered) {
-      a.X = r.xg + (long)(s & 1) * r.B * ldg;
-      a.ldx = ldg;
-      a.idx = nullptr;
-      a.Y = r.yg + (long)(s & 1) * r.B;
-      if (xbg) {
-        a.X = reinterpret_cast<const float*>(xbg + (long)(s & 1) * r.B * ldb);
-        a.ldx = ldb / 2;
-        a.packed = true;
-      }
-    }
+    if (r.xg && s > 0) gather_read(a, ga, bufs, s);
     int st = step_dispatch(0, r.prec, a, stream);
     if (st) return st;
     if (r.dp_clip > 0.f)
@@ -1976,49 +1933,30 @@ ECG_API int ecg_tiny_cohort_round_sizeof(void) { return (int)sizeof(EcgTinyCohor
 
 namespace {
 
-// (The cohort kernels are first named here, behind every older launch site, so that they are instantiated last.)
-// One cohort step launch (MODE 3): grid (a.B, M), ``a.params`` / ``a.wprep`` client 0's, ``a.out`` the M * a.B-row slab.
-template <int WAVES, bool F32, bool PF, bool PK = false>
-int launch_cohort_step(const StepArgs& a, int M, hipStream_t stream) {
-  const Smem sm = make_smem(a.L, WAVES, a.nc, F32);
-  auto kern = tiny_ecg_step_kernel<WAVES, 3, F32, PF, PK>;
-  if (sm.bytes > 64 * 1024)
-    ECG_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, sm.bytes));
-  if (PK && a.idx) return ecg::kBadArg;  // the PK kernel reads row b
-  hipLaunchKernelGGL(kern, dim3(a.B, M), dim3(WAVES * 64), sm.bytes, stream, a.X, a.ldx, PF ? a.wprep : nullptr, a.Y,
-                     g_stamps, a.L, a.nc, a.params, a.out, a.out_stride, a.inv_B, a.idx, no_fuse().slab_wt);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
+// (The cohort kernels - MODE 3 and slab_reduce_cohort_sgd_kernel - are first named here, behind every older launch
+// site, so that they are instantiated last.)
 // The cohort forms of the three kernels a production round launches: fp32; bf16 building its operands in LDS (a
 // round's first step: ``a.wprep`` null); bf16 on packed rows and the images (``a.packed``).  Arguments are checked
 // by check_cohort_round.
 int cohort_step_dispatch(int prec, const StepArgs& a, int M, hipStream_t stream) {
   const bool w8 = pick_waves(a.L, prec == 1) == 8;
-  if (prec == 1) return w8 ? launch_cohort_step<8, true, false>(a, M, stream) : launch_cohort_step<16, true, false>(a, M, stream);
+  if (prec == 1)
+    return w8 ? launch_step<8, 3, true, false>(a, stream, M) : launch_step<16, 3, true, false>(a, stream, M);
   if (a.packed)
-    return w8 ? launch_cohort_step<8, false, true, true>(a, M, stream)
-              : launch_cohort_step<16, false, true, true>(a, M, stream);
+    return w8 ? launch_step<8, 3, false, true, true>(a, stream, M) : launch_step<16, 3, false, true, true>(a, stream, M);
   if (a.wprep) return ecg::kBadArg;  // the unpacked prepared-fragment kernel has no cohort form
-  return w8 ? launch_cohort_step<8, false, false>(a, M, stream) : launch_cohort_step<16, false, false>(a, M, stream);
+  return w8 ? launch_step<8, 3, false, false>(a, stream, M) : launch_step<16, 3, false, false>(a, stream, M);
 }
 
 // The cohort reduce + SGD of one step: M x the plain reduce's blocks, then the gather blocks of the next step.
 int cohort_reduce_dispatch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
                            float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
                            hipStream_t stream, const GatherArgs* gather = nullptr) {
-  constexpr int cols = kRedColsDefault;
-  const int nred = M * ((P + cols) / cols);
-  GatherArgs ga{};
-  int grid = nred;
-  if (gather) {
-    ga = *gather;
-    const int rpb = gather_rows_per_block(ga.L, ga.vec, cols * RED_ROWG);
-    grid += (ga.B + rpb - 1) / rpb;
-  }
-  hipLaunchKernelGGL(slab_reduce_cohort_sgd_kernel<cols>, dim3(grid), dim3(cols * RED_ROWG), 0, stream, slab, params,
-                     mom, nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc, ga);
+  const int st = check_reduce(G, stride, P, 1, params, momentum, mom);
+  if (st) return st;
+  const RedGeom g = red_geom(P, M, gather, true);
+  hipLaunchKernelGGL(slab_reduce_cohort_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
+                     params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc, g.ga);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -2043,33 +1981,22 @@ static int check_cohort_round(const EcgTinyCohortRound* r) {
 static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream) {
   const int P = make_layout(r.nc).P, rows = r.M * r.B;
   unsigned char* wprep = static_cast<unsigned char*>(r.wprep);
-  const int ldg = (r.L + 3) / 4 * 4, ldb = pack_ldb(r.L);
-  __bf16* xbg = static_cast<__bf16*>(r.xbg);
+  const GatherBufs bufs{r.xg, r.yg, static_cast<__bf16*>(r.xbg)};  // M * B rows each (bf16: all three, fp32: none)
   const bool bf16 = r.prec == 0;
   if (r.fanout) {
     hipLaunchKernelGGL(cohort_fanout_kernel<256>, dim3((P + 255) / 256, r.M), dim3(256), 0, stream, r.global_params,
                        r.params, r.mom, P);
     ECG_HIP_CHECK(hipGetLastError());
   }
-  GatherArgs ga{r.X, r.ldx, nullptr, r.Y, nullptr, nullptr, r.L, ldg, rows,
-                (r.L % 4 == 0 && r.ldx % 4 == 0 && reinterpret_cast<uintptr_t>(r.X) % 16 == 0) ? 1 : 0, nullptr, ldb};
+  GatherArgs ga = gather_args(r.X, r.ldx, r.Y, r.L, rows);
   for (int s = 0; s < r.steps; ++s) {
     const int* idx = r.idx + (long)s * rows;
     const bool gather_next = bf16 && s + 1 < r.steps;
-    if (gather_next) {  // ping-pong buffers as in enqueue_round, M * B rows each
-      ga.idx = idx + rows;
-      ga.xg = r.xg + (long)((s + 1) & 1) * rows * ldg;
-      ga.yg = r.yg + (long)((s + 1) & 1) * rows;
-      ga.xbg = xbg + (long)((s + 1) & 1) * rows * ldb;
-    }
+    if (gather_next) gather_fill(ga, bufs, s, idx + rows);
     StepArgs a{r.X, r.L, r.ldx, idx, r.Y, r.params, r.nc, r.slab, r.slab_stride, r.B, 1.0f / (float)r.B, nullptr};
     if (bf16 && s > 0) {
-      a.X = reinterpret_cast<const float*>(xbg + (long)(s & 1) * rows * ldb);
-      a.ldx = ldb / 2;
-      a.idx = nullptr;
-      a.Y = r.yg + (long)(s & 1) * rows;
+      gather_read(a, ga, bufs, s);
       a.wprep = wprep;
-      a.packed = true;
     }
     int st = cohort_step_dispatch(r.prec, a, r.M, stream);
     if (st) return st;
