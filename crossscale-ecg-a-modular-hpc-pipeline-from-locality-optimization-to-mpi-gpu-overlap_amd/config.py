@@ -57,6 +57,15 @@ class FedAvgConfig:
     clients_per_gpu: int = 1
     cohort: int = 0
     cohort_csv: str = "results/fedavg_cohort.csv"
+    # client-level DP on a cohort round (off by default; needs clients_per_gpu > 1): every client's round delta is
+    # clipped to l2 norm client_dp_clip, the clipped deltas are averaged, Gaussian noise with multiplier client_dp_noise
+    # is added and the result is applied with the server step size server_lr (usable without a clip); with a clip rank 0
+    # appends the cumulative client-level epsilon at client_dp_delta per round to client_privacy_csv
+    client_dp_clip: float = 0.0
+    client_dp_noise: float = 0.0
+    client_dp_delta: float = 1e-5
+    server_lr: float = 1.0
+    client_privacy_csv: str = "results/fedavg_client_privacy.csv"
     results_csv: str = "results/fedavg_results.csv"
     jsonl: Optional[str] = None
     model: str = "tiny_ecg"

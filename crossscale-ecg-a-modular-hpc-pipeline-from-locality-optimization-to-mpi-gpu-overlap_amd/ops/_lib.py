@@ -75,7 +75,9 @@ class TinyCohortRound(C.Structure):
     _fields_ = [("X", vp), ("ldx", i64), ("idx", vp), ("Y", vp), ("params", vp), ("mom", vp), ("slab", vp),
                 ("loss_acc", vp), ("wprep", vp), ("xg", vp), ("yg", vp), ("xbg", vp), ("global_params", vp),
                 ("L", i32), ("nc", i32), ("slab_stride", i32), ("B", i32), ("steps", i32), ("M", i32),
-                ("fanout", i32), ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32)]
+                ("fanout", i32), ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32),
+                ("cdp_clip", f32), ("cdp_sigma", f32), ("server_lr", f32), ("cdp_seed", u64), ("cdp_scale", vp),
+                ("cdp_norm", vp), ("cdp_round", vp)]
 
 
 def _bind_kernels(lib: C.CDLL) -> None:
@@ -104,6 +106,8 @@ def _bind_kernels(lib: C.CDLL) -> None:
                           "in ops/_lib.py: rebuild the library (python csrc/build.py) or update TinyCohortRound")
     _sig(lib, "ecg_tiny_cohort_round_enqueue", [C.POINTER(TinyCohortRound), vp])
     _sig(lib, "ecg_tiny_cohort_round_capture", [C.POINTER(vp), C.POINTER(TinyCohortRound)])
+    _sig(lib, "ecg_cohort_dp_close", [vp, vp, i32, i32, f32, f32, f32, u64, vp, vp, vp, vp])
+    _sig(lib, "ecg_cohort_dp_noise", [vp, i32, u64, u64, vp])
     _sig(lib, "ecg_tiny_cohort_param_stride", [i32])
     _sig(lib, "ecg_tiny_cohort_wprep_stride", [])
     _sig(lib, "ecg_tiny_gather_floats", [i32, i32], i64)

@@ -8,12 +8,18 @@ cohort order into the global weights - captured into one hipGraph like a single 
 no state between rounds (weights from the global model, zero momentum), and which clients and rows a round uses is a
 pure function of ``(seed, round)`` (``data.dataset.CohortSampler``).  Limits: no DP-SGD in a cohort, equal client
 sizes, plain (unweighted) mean.
+
+Client-level DP (``client_dp_clip`` > 0; DP-FedAvg) and a server step size ``server_lr`` != 1 close the round with
+``cohort_delta_scale_kernel`` + ``cohort_dp_mean_kernel`` in place of the mean: every client's round delta clipped to
+l2 norm C, averaged, Gaussian noise of standard deviation ``sigma * C / (M * sqrt(world_size))`` per parameter added,
+the result applied with step size ``server_lr`` (``train/cohort.py`` states the definition).  The noise is a function
+of ``(client_dp_seed, round, parameter index)``; the round counter the kernels read is a device word this trainer owns.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -22,6 +28,7 @@ from ..data.dataset import CohortSampler
 from ..models.tiny_ecg import TinyECG, num_params
 from .fused_tiny import _check_dataset, labels_int32, prec_id, slab_stride
 from .tiny_eval import EvalResult, TinyEvaluator, tiny_evaluate
+from ..train.cohort import check_client_dp, client_dp_seed_of, client_dp_sigma_share
 
 
 class FusedCohortTrainer:
@@ -31,10 +38,13 @@ class FusedCohortTrainer:
     def __init__(self, model: TinyECG, x_gpu: torch.Tensor, y_gpu: torch.Tensor, batch_size: int,
                  steps_per_round: int, clients: int, cohort: Optional[int] = None, lr: float = 1e-2,
                  momentum: float = 0.9, weight_decay: float = 0.0, nesterov: bool = False, seed: Optional[int] = None,
-                 use_graph: Optional[bool] = None, precision: str = "bf16", dp_clip: float = 0.0):
+                 use_graph: Optional[bool] = None, precision: str = "bf16", dp_clip: float = 0.0,
+                 client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
+                 server_lr: float = 1.0, world_size: int = 1):
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients: the cohort "
                              "reduce has no per-sample clip")
+        check_client_dp(client_dp_clip, client_dp_noise, server_lr, world_size)
         self.device = x_gpu.device
         self.precision = precision
         self.prec = prec_id(precision)
@@ -84,12 +94,27 @@ class FusedCohortTrainer:
         self.use_graph = (os.environ.get("ECG_TINY_GRAPH", "1") != "0") if use_graph is None else bool(use_graph)
         self._graphs = {}
         self._evaluator: Optional[TinyEvaluator] = None
+        # client-level DP / server step size: the clip factors and delta norms of the last round and the round counter
+        # the close draws its noise from (a device word: kernel arguments are baked into a captured graph)
+        self.cdp_clip, self.cdp_noise, self.server_lr = float(client_dp_clip), float(client_dp_noise), float(server_lr)
+        self.cdp_seed = client_dp_seed_of(seed, client_dp_seed)
+        self.client_dp = self.cdp_clip > 0.0 or self.server_lr != 1.0
+        self.cdp_scale = self.cdp_norm = self.cdp_round = None
+        if self.client_dp:
+            self.cdp_scale = torch.ones(self.M, **f32)
+            self.cdp_norm = torch.zeros(self.M, **f32)
+            self.cdp_round = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._round = _lib.TinyCohortRound(
             X=self.x.data_ptr(), ldx=self.x.stride(0), Y=self.y32.data_ptr(), params=self.cparams.data_ptr(),
             mom=self.cmom.data_ptr(), slab=self.slab.data_ptr(), loss_acc=self.loss_acc.data_ptr(),
             wprep=_lib.ptr(self.wprep), xg=_lib.ptr(self.xg), yg=_lib.ptr(self.yg), xbg=_lib.ptr(self.xbg),
             global_params=self.params.data_ptr(), L=L, nc=self.nc, slab_stride=self.stride, B=self.B, M=self.M,
             fanout=1, lr=self.lr, momentum=self.momentum, wd=self.wd, nesterov=int(self.nesterov), prec=self.prec)
+        if self.client_dp:  # (all-zero fields otherwise: the round then issues the launches it always issued)
+            r = self._round
+            r.cdp_clip, r.cdp_sigma = self.cdp_clip, client_dp_sigma_share(self.cdp_noise, world_size)
+            r.server_lr, r.cdp_seed = self.server_lr, self.cdp_seed
+            r.cdp_scale, r.cdp_norm, r.cdp_round = (t.data_ptr() for t in (self.cdp_scale, self.cdp_norm, self.cdp_round))
 
     # ------------------------------------------------------------------ graph management
     def _round_of(self, n: int, table: torch.Tensor):
@@ -123,13 +148,15 @@ class FusedCohortTrainer:
     # ------------------------------------------------------------------ execution
     def prepare(self, sizes) -> None:
         """Capture, upload and warm every round graph whose step count is in ``sizes`` (on both index tables).  The
-        warm-up replays are rolled back: global weights, loss words, tables and the round counter stay as found (the
-        per-client buffers are scratch that every round's fan-out rewrites)."""
+        warm-up replays are rolled back: global weights, loss words, tables and the round counter - the device word of
+        the DP close with it - stay as found (the per-client buffers are scratch that every round's fan-out rewrites)."""
         if not self.use_graph:
             return
         lib = _lib.kernels()
         sizes = [self._check_n(n) for n in sizes]
         state = (self.params, self.loss_acc, self.idx_stage, self.idx_table)
+        if self.client_dp:
+            state += (self.cdp_round, self.cdp_scale, self.cdp_norm)
         snap = [t.clone() for t in state]
         stream = _lib.stream_ptr(self.device)
         for n in sizes:
@@ -148,10 +175,19 @@ class FusedCohortTrainer:
         return n
 
     def set_cohort_round(self, r: int) -> None:
-        """Continue at round ``r`` (checkpoint resume): the next staging draws that round's cohort."""
+        """Continue at round ``r`` (checkpoint resume): the next staging draws that round's cohort, and the DP close
+        that round's noise."""
         if self._staged is not None:
             raise RuntimeError("a round is staged: set the round counter before staging")
         self.cohort_round = int(r)
+        if self.cdp_round is not None:
+            self.cdp_round.fill_(int(r))
+
+    def last_clip_stats(self) -> Tuple[List[float], float]:
+        """(the last round's delta norms in cohort order, the share of its clients that were clipped); synchronises."""
+        if not self.client_dp:
+            return [], 0.0
+        return self.cdp_norm.tolist(), float((self.cdp_scale < 1.0).float().mean().item())
 
     def stage(self, n_steps: Optional[int] = None) -> None:
         """Draw the next round's cohort and batches into the staging table (a round of ``n_steps`` < S steps reads

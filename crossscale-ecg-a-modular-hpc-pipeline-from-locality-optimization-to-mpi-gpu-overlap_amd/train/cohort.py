@@ -5,25 +5,42 @@ Per round: the cohort and its batches from the same ``CohortSampler`` (same ``(s
 device); for every cohort client a copy of the global weights, ``S`` plain SGD steps with zero initial momentum on its
 columns of the table, then ``global = (((p_0 + p_1) + ...) + p_{M-1}) * fp32(1 / M)`` in ascending cohort order,
 written into the model's parameters (its flat buffer when it has one).
+
+Client-level DP (``client_dp_clip`` C > 0; DP-FedAvg) and a server step size ``server_lr`` eta != 1 replace that mean:
+with g the global weights the round started from, ``d_c = p_c - g`` over all P parameters, ``n_c = |d_c|_2`` and
+``s_c = min(1, C / n_c)`` (``n_c == 0 -> 1``; C == 0: no clipping),
+
+    g_new = g + eta * ((((s_0 d_0 + s_1 d_1) + ...) + s_{M-1} d_{M-1}) * fp32(1 / M) + nu * z)
+
+in fp32, ``nu = fp32(sigma * C / (M * sqrt(W)))`` with sigma = ``client_dp_noise`` and W = ``world_size`` (the driver
+averages W ranks' weights, which leaves noise of standard deviation sigma * C / (M * W) on a mean of sensitivity
+C / (M * W)), and ``z = philox.normal(client_dp_seed, round, P, stream=1)``: the definition that
+``cohort_dp_mean_kernel`` of csrc/kernels/tiny_ecg_step.hip implements.
 """
 from __future__ import annotations
 
 import copy
-from typing import List, Optional
+import math
+from typing import List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
 from ..data.dataset import CohortSampler
+from ..utils import philox
 
 
 class TorchCohortTrainer:
     def __init__(self, model: torch.nn.Module, x: torch.Tensor, y: torch.Tensor, batch_size: int,
                  steps_per_round: int, clients: int, cohort: Optional[int] = None, lr: float = 1e-2,
                  momentum: float = 0.9, weight_decay: float = 0.0, nesterov: bool = False,
-                 amp_dtype: Optional[torch.dtype] = None, seed: Optional[int] = None, dp_clip: float = 0.0):
+                 amp_dtype: Optional[torch.dtype] = None, seed: Optional[int] = None, dp_clip: float = 0.0,
+                 client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
+                 server_lr: float = 1.0, world_size: int = 1):
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients")
+        check_client_dp(client_dp_clip, client_dp_noise, server_lr, world_size)
         self.model, self.x, self.y = model, x, y
         self.device = x.device
         self.B, self.S, self.K = int(batch_size), int(steps_per_round), int(clients)
@@ -41,6 +58,12 @@ class TorchCohortTrainer:
         self.round_clients: List[int] = []
         self.steps_done = 0
         self.precision = "fp32" if amp_dtype is None else str(amp_dtype).replace("torch.", "").replace("bfloat16", "bf16")
+        self.cdp_clip, self.cdp_noise, self.server_lr = float(client_dp_clip), float(client_dp_noise), float(server_lr)
+        self.cdp_seed = client_dp_seed_of(seed, client_dp_seed)
+        self.cdp_nu = client_dp_nu(self.cdp_noise, self.cdp_clip, self.M, world_size)
+        self.client_dp = self.cdp_clip > 0.0 or self.server_lr != 1.0
+        self._norms: List[float] = []
+        self._scales: List[float] = []
 
     def set_cohort_round(self, r: int) -> None:
         self.cohort_round = int(r)
@@ -64,18 +87,51 @@ class TorchCohortTrainer:
             self.loss_acc += loss.detach().float()
         return [p.detach().clone() for p in self.work.parameters()]
 
-    def run_table(self, n: int, table: torch.Tensor) -> None:
-        """One cohort round on ``table`` (int32 ``[>= n, M * B]``): the clients one after another, then the mean."""
-        total = None
-        for j in range(self.M):
-            ps = self._client_round(j, n, table)
-            total = ps if total is None else [t + p for t, p in zip(total, ps)]
-        inv = torch.tensor(1.0 / self.M, dtype=torch.float32, device=self.device)  # fp32(1 / M), rounded once
-        with torch.no_grad():
-            for pg, t in zip(self.model.parameters(), total):
-                pg.copy_(t * inv)
+    def run_table(self, n: int, table: torch.Tensor, r: Optional[int] = None) -> None:
+        """One cohort round on ``table`` (int32 ``[>= n, M * B]``): the clients one after another, then the mean (or
+        the DP close, which draws the noise of round ``r``; default: the round counter)."""
+        if self.client_dp:
+            self._run_table_client_dp(n, table, self.cohort_round if r is None else r)
+        else:
+            total = None
+            for j in range(self.M):
+                ps = self._client_round(j, n, table)
+                total = ps if total is None else [t + p for t, p in zip(total, ps)]
+            inv = torch.tensor(1.0 / self.M, dtype=torch.float32, device=self.device)  # fp32(1 / M), rounded once
+            with torch.no_grad():
+                for pg, t in zip(self.model.parameters(), total):
+                    pg.copy_(t * inv)
         self.steps_done += n
         self._loss_steps += n
+
+    def _run_table_client_dp(self, n: int, table: torch.Tensor, r: int) -> None:
+        """The DP close of round ``r`` (the module docstring's definition), everything in fp32."""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        g = torch.cat([p.detach().reshape(-1) for p in self.model.parameters()]).float()
+        acc, self._norms, self._scales = None, [], []
+        for j in range(self.M):
+            d = torch.cat([p.reshape(-1) for p in self._client_round(j, n, table)]).float() - g
+            nrm = torch.linalg.vector_norm(d)
+            sc = torch.ones((), **f32)
+            if self.cdp_clip > 0.0 and float(nrm) > 0.0:
+                sc = torch.minimum(sc, torch.tensor(self.cdp_clip, **f32) / nrm)
+            self._norms.append(float(nrm))
+            self._scales.append(float(sc))
+            acc = sc * d if acc is None else acc + sc * d
+        upd = acc * torch.tensor(1.0 / self.M, **f32)
+        if self.cdp_nu != 0.0:
+            z = philox.normal(self.cdp_seed, r, g.numel(), stream=1).astype(np.float32)
+            upd = upd + torch.tensor(self.cdp_nu, **f32) * torch.from_numpy(z).to(self.device)
+        new = g + torch.tensor(self.server_lr, **f32) * upd
+        off = 0
+        with torch.no_grad():
+            for pg in self.model.parameters():
+                pg.copy_(new[off:off + pg.numel()].view_as(pg))
+                off += pg.numel()
+
+    def last_clip_stats(self) -> Tuple[List[float], float]:
+        """(the last round's delta norms in cohort order, the share of its clients that were clipped)."""
+        return list(self._norms), sum(s < 1.0 for s in self._scales) / max(1, len(self._scales))
 
     def run_steps(self, n: int, reset_loss: bool = True) -> None:
         self.prepare_round(n, reset_loss)
@@ -91,7 +147,33 @@ class TorchCohortTrainer:
     def launch_round(self, n: int, next_n=None) -> None:
         self.round_clients = self.sampler.fill(self.cohort_round, self.table)
         self.cohort_round += 1
-        self.run_table(n, self.table)
+        self.run_table(n, self.table, self.cohort_round - 1)
 
     def avg_loss(self) -> float:
         return float(self.loss_acc.item()) / (self.M * max(1, self._loss_steps))
+
+
+def check_client_dp(clip: float, noise: float, server_lr: float, world_size: int) -> None:
+    if clip < 0 or noise < 0:
+        raise ValueError("client_dp_clip and client_dp_noise must be >= 0")
+    if noise > 0 and clip == 0:
+        raise ValueError("client_dp_noise needs client_dp_clip > 0: the noise is scaled by the clip norm")
+    if not server_lr > 0:
+        raise ValueError("server_lr must be > 0")
+    if world_size < 1:
+        raise ValueError("world_size must be >= 1")
+
+
+def client_dp_seed_of(seed: Optional[int], client_dp_seed: Optional[int]) -> int:
+    """The 64-bit Philox key of the client-level noise: ``client_dp_seed``, by default a mix of the trainer's seed."""
+    return (philox.mix64(0 if seed is None else seed) if client_dp_seed is None else int(client_dp_seed)) & philox.MASK64
+
+
+def client_dp_sigma_share(noise: float, world_size: int) -> float:
+    """sigma / sqrt(W): the noise multiplier of one rank's share (what the native round takes as ``cdp_sigma``)."""
+    return float(noise) / math.sqrt(world_size)
+
+
+def client_dp_nu(noise: float, clip: float, cohort: int, world_size: int) -> float:
+    """nu = sigma * C / (M * sqrt(W)): the standard deviation of the noise a rank adds per parameter."""
+    return float(np.float32(client_dp_sigma_share(noise, world_size) * float(clip) / cohort))

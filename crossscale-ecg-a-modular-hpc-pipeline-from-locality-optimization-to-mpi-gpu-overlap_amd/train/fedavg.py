@@ -41,6 +41,15 @@ MI355X execution (vs the reference's host-staged per-tensor MPI calls and per-st
     eager reference.  ``samples_per_s`` counts all M * B * S windows of a round; ``batch_size`` in the round rows stays
     the per-client B; rank 0 appends the cohort's shape per round to ``--cohort-csv``.  TinyECG only; not combined
     with DP-SGD, ``--sync ddp``, ``--drop-prob`` (client sampling replaces it) or ``--overlap delayed``.
+  * ``--client-dp-clip C`` / ``--client-dp-noise sigma`` / ``--client-dp-delta delta`` / ``--server-lr eta``: client-level
+    DP on a cohort round (DP-FedAvg; needs ``--clients-per-gpu``).  Every rank clips each of its M clients' round
+    deltas to l2 norm C, averages them, adds N(0, (sigma C / (M sqrt(W)))^2) per parameter and applies the result to the
+    global weights with step size eta; the unchanged all-reduce(AVG) of the W ranks' weights then holds the clipped mean
+    over all W * M clients plus noise of standard deviation sigma C / (M W): noise multiplier sigma at sensitivity
+    C / (M W).  Without that all-reduce (``--sync none``, one process) W is 1: every rank adds the whole sigma C / M.  Every rank's noise key is the 64-bit mix of ``seed + 7919 * rank``.  Rank 0 appends the cumulative
+    epsilon per round (``utils.privacy`` at ``sample_rate = M / K``, one composition per round: the Poisson-subsampling
+    bound applied to fixed-size sampling without replacement - an approximation, as for DP-SGD) with rank 0's median
+    client norm and clipped share to ``--client-privacy-csv``.  ``avg_loss`` and the evaluation metrics are not private.
 """
 from __future__ import annotations
 
@@ -65,7 +74,7 @@ from ..utils import profiling, usable_cpus
 from ..utils.ckpt import (ckpt_path, save_checkpoint, load_checkpoint, latest_checkpoint, rank_state_path,
                           save_rank_state, load_trainer_local_state)
 from ..utils.csvio import (RoundStats, append_results, ROUND_COLUMNS, EVAL_COLUMNS, PRIVACY_COLUMNS,
-                           COHORT_COLUMNS)
+                           COHORT_COLUMNS, CLIENT_PRIVACY_COLUMNS)
 from ..utils.philox import mix64
 from ..utils.privacy import epsilon as dp_epsilon
 from ..utils.log import RankLogger
@@ -204,12 +213,40 @@ def check_cohort_config(cfg: FedAvgConfig, backend: str) -> None:
                          "starts from the averaged weights of the round before")
 
 
+def check_client_dp_config(cfg: FedAvgConfig) -> None:
+    """Client-level DP and the server step size act on a cohort round: they need client sampling (and with it
+    everything ``check_cohort_config`` asks for)."""
+    if cfg.client_dp_clip < 0 or cfg.client_dp_noise < 0:
+        raise ValueError("--client-dp-clip and --client-dp-noise must be >= 0")
+    if cfg.client_dp_noise > 0 and cfg.client_dp_clip == 0:
+        raise ValueError("--client-dp-noise needs --client-dp-clip > 0: the noise is scaled by the clip norm")
+    if not cfg.server_lr > 0:
+        raise ValueError("--server-lr must be > 0")
+    if cfg.client_dp_clip == 0 and cfg.server_lr == 1.0:
+        return
+    if cfg.clients_per_gpu <= 1:
+        raise ValueError("--client-dp-clip / --client-dp-noise / --server-lr need client sampling (--clients-per-gpu "
+                         "K > 1): they clip, noise and scale the mean of a cohort's client deltas")
+    if cfg.client_dp_clip > 0 and not 0.0 < cfg.client_dp_delta < 1.0:
+        raise ValueError("--client-dp-delta must be in (0, 1)")
+
+
+def client_dp_world(cfg: FedAvgConfig, ctx: DistContext) -> int:
+    """The number of ranks whose weights the driver averages after a round: every rank adds sigma / sqrt(that) of the
+    client-level noise.  Only ``--sync fedavg`` on more than one rank averages; an independent client (``--sync none``, a
+    single process) keeps its own weights and must add the whole of the noise itself."""
+    return ctx.world_size if (cfg.sync == "fedavg" and ctx.distributed) else 1
+
+
 def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistContext, backend: str):
     seed = cfg.seed + 7919 * ctx.rank
     check_dp_config(cfg, config_name, backend)
     check_cohort_config(cfg, backend)
+    check_client_dp_config(cfg)
     if cfg.clients_per_gpu > 1:
-        kw = dict(clients=cfg.clients_per_gpu, cohort=cohort_size(cfg), lr=cfg.lr, momentum=cfg.momentum, seed=seed)
+        kw = dict(clients=cfg.clients_per_gpu, cohort=cohort_size(cfg), lr=cfg.lr, momentum=cfg.momentum, seed=seed,
+                  client_dp_clip=cfg.client_dp_clip, client_dp_noise=cfg.client_dp_noise, client_dp_seed=mix64(seed),
+                  server_lr=cfg.server_lr, world_size=client_dp_world(cfg, ctx))
         if backend == "fused":
             from ..ops.fused_cohort import FusedCohortTrainer
             prec = "bf16" if (config_name == "G1" and cfg.amp_dtype == "bf16") else "fp32"
@@ -337,6 +374,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
     for cname in configs:  # an unsupported DP-SGD combination stops the run before any configuration trains
         check_dp_config(cfg, cname, pick_backend(cfg, cname, ctx))
         check_cohort_config(cfg, pick_backend(cfg, cname, ctx))
+    check_client_dp_config(cfg)
     M = cohort_size(cfg)  # clients trained per GPU and round (1: no client sampling)
     all_rows: List[Dict] = []
     fcomm = FedAvgComm(ctx)
@@ -364,6 +402,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         evals = []  # (round, summed record, this rank's eval_ms) per evaluated round
         privacy = []  # DP-SGD: this client's cumulative (round, steps, epsilon)
         cohorts = []  # client sampling: (round, this rank's drawn client ids)
+        client_privacy = []  # client-level DP, rank 0: (round, median client norm, clipped share)
         sample_rate = cfg.batch_size / x.shape[0]
         for r in range(start_round, cfg.rounds):
             t_round0 = time.perf_counter()
@@ -426,6 +465,9 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                         save_checkpoint(ckpt_path(cfg.ckpt_dir, r, cname), r, model, mom, cname, asdict(cfg))
                 save_rank_state(cfg.ckpt_dir, r, cname, ctx.rank, trainer, client_weights=own)
             recs.append((r, rec, m_l0, m_l1, inner, avg_loss, (time.perf_counter() - t_round0) * 1e3))
+            if cfg.client_dp_clip > 0 and ctx.rank == 0:  # (avg_loss synchronised: the round's norms are there)
+                norms, clipped = trainer.last_clip_stats()
+                client_privacy.append((r, float(np.median(norms)), clipped))
             if eval_due:  # after the round's wall clock stopped; the stream is idle (avg_loss synchronised)
                 _sync(dev)
                 t_e0 = time.perf_counter()
@@ -486,6 +528,23 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                 append_results(crows, cfg.cohort_csv, COHORT_COLUMNS)
             for row in crows:
                 log.event("cohort", **row)
+        if client_privacy:
+            cprows = [{"config": cname, "world_size": ctx.world_size, "round_idx": r,
+                       "sample_rate": M / cfg.clients_per_gpu, "noise_multiplier": cfg.client_dp_noise,
+                       "clip_norm": cfg.client_dp_clip, "delta": cfg.client_dp_delta,
+                       "epsilon": dp_epsilon(cfg.client_dp_noise, M / cfg.clients_per_gpu, r + 1, cfg.client_dp_delta),
+                       "median_client_norm": med, "clipped_share_rank0": clipped}
+                      for r, med, clipped in client_privacy]
+            if cfg.client_privacy_csv:
+                append_results(cprows, cfg.client_privacy_csv, CLIENT_PRIVACY_COLUMNS)
+            for row in cprows:
+                log.event("client_privacy", **row)
+            last = cprows[-1]
+            log.info(f"[client-privacy] {cname}: after round {last['round_idx']} (q = M/K = {last['sample_rate']:.4g}, "
+                     f"sigma={cfg.client_dp_noise:g}, C={cfg.client_dp_clip:g}, server lr {cfg.server_lr:g}) client-level "
+                     f"epsilon <= {last['epsilon']:.4g} at delta={cfg.client_dp_delta:g} (Poisson-subsampling bound "
+                     "applied to fixed-size sampling without replacement: an approximation; avg_loss and the evaluation "
+                     "metrics are not private)")
         gathered = comm.gather(rows, root=0)
         if ctx.rank == 0:
             flat_rows = [row for rl in gathered for row in rl]

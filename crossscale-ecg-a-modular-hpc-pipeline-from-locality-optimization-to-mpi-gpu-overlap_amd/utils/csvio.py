@@ -63,6 +63,11 @@ PRIVACY_COLUMNS = ["config", "world_size", "round_idx", "steps", "sample_rate", 
 
 COHORT_COLUMNS = ["config", "world_size", "round_idx", "clients_per_gpu", "cohort", "batch_size",
                   "windows_per_round_per_gpu", "clients_rank0"]
+# one row per (config, round) of a client-level DP run (--client-dp-clip): the cumulative epsilon after that round at
+# sample_rate = cohort / clients_per_gpu (utils/privacy.py: the Poisson-subsampling bound applied to fixed-size sampling
+# without replacement), and rank 0's median client delta norm and share of clipped clients in that round
+CLIENT_PRIVACY_COLUMNS = ["config", "world_size", "round_idx", "sample_rate", "noise_multiplier", "clip_norm", "delta",
+                          "epsilon", "median_client_norm", "clipped_share_rank0"]
 LOCALITY_COLUMNS = ["config", "batch_size", "pin_memory", "contiguous", "non_blocking", "data_ms", "h2d_ms",
                     "compute_ms", "step_ms", "samples_per_s"]
 LABL_COLUMNS = ["config", "batch_size", "step_ms", "samples_per_s", "data_ms", "h2d_ms", "compute_ms"]

@@ -4,8 +4,10 @@ Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 
 paper and checked against the Random123 known-answer vectors (tests/test_philox_cpu.py).  Conventions, the same as
 ``dp_normal`` in csrc/kernels/tiny_ecg_step.hip:
 
-* counter ``(i, t & 0xffffffff, t >> 32, 0)``, key ``(seed & 0xffffffff, seed >> 32)``: ``i`` the flat parameter
-  index, ``t`` the 64-bit DP step counter, ``seed`` the 64-bit DP seed;
+* counter ``(i, t & 0xffffffff, t >> 32, stream)``, key ``(seed & 0xffffffff, seed >> 32)``: ``i`` the flat parameter
+  index, ``t`` the 64-bit DP step counter, ``seed`` the 64-bit DP seed; ``stream`` is 0 for DP-SGD (``dp_normal``) and
+  1 for the client-level DP close of a cohort round (``cohort_dp_normal``, ``t`` the round counter), so the two
+  noise streams never share a counter;
 * ``u1 = ((w0 >> 8) + 1) * 2^-24`` in (0, 1], ``u2 = (w1 >> 8) * 2^-24`` in [0, 1) from output words 0 and 1 (both
   exact in fp32);
 * ``z = sqrt(-2 ln u1) * cos(2 pi u2)`` (Box-Muller, one normal per counter; ``|z| <= sqrt(48 ln 2) < 5.77``).
@@ -39,27 +41,28 @@ def philox4x32_10(counter, key) -> np.ndarray:
     return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
 
 
-def words(seed: int, t: int, n: int) -> np.ndarray:
-    """Output words uint32 [n, 4] of parameter indices 0..n-1 at step ``t``."""
+def words(seed: int, t: int, n: int, stream: int = 0) -> np.ndarray:
+    """Output words uint32 [n, 4] of parameter indices 0..n-1 at step ``t`` of noise stream ``stream``."""
     seed, t = int(seed) & MASK64, int(t) & MASK64
     ctr = np.zeros((n, 4), dtype=np.uint64)
     ctr[:, 0] = np.arange(n, dtype=np.uint64)
     ctr[:, 1] = t & MASK32
     ctr[:, 2] = t >> 32
+    ctr[:, 3] = int(stream) & MASK32
     return philox4x32_10(ctr, (seed & MASK32, seed >> 32))
 
 
-def uniforms(seed: int, t: int, n: int):
+def uniforms(seed: int, t: int, n: int, stream: int = 0):
     """(u1 in (0, 1], u2 in [0, 1)) as float64 arrays [n]; every value is a multiple of 2^-24."""
-    w = words(seed, t, n)
+    w = words(seed, t, n, stream)
     u1 = ((w[:, 0] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
     u2 = (w[:, 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
     return u1, u2
 
 
-def normal(seed: int, t: int, n: int) -> np.ndarray:
-    """Standard normals float64 [n] of parameter indices 0..n-1 at step ``t``."""
-    u1, u2 = uniforms(seed, t, n)
+def normal(seed: int, t: int, n: int, stream: int = 0) -> np.ndarray:
+    """Standard normals float64 [n] of parameter indices 0..n-1 at step ``t`` of noise stream ``stream``."""
+    u1, u2 = uniforms(seed, t, n, stream)
     return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
 
 

@@ -25,6 +25,7 @@
 #include "../include/ecg_common.h"
 #include "../include/tiny_ecg.h"
 
+#include <cfloat>
 #include <climits>
 #include <cstdint>
 #include <cstdlib>
@@ -1428,6 +1429,77 @@ __global__ __launch_bounds__(NT) void cohort_mean_kernel(const float* __restrict
   global_params[i] = s * inv_M;
 }
 
+// ---------------------------------------------------------------------------- client-level DP (DP-FedAvg close)
+// The close of a cohort round with client-level differential privacy, in place of cohort_mean_kernel: with g the
+// round's starting weights (what the fan-out read: ``global_params`` is untouched until here), d_c = p_c - g,
+// n_c = |d_c|_2 and s_c = min(1, C / n_c) (n_c == 0 -> 1),
+//   g_new[i] = g[i] + eta * ((((s_0 d_0[i] + s_1 d_1[i]) + ...) + s_{M-1} d_{M-1}[i]) * inv_M + nu * z_i),
+// clients in ascending order in fp32, nu = sigma * C / M rounded once on the host (nu == 0: nothing is drawn).
+// (Templates, like the DP and cohort kernels: emitted after every older kernel.)
+//
+// z_i: dp_normal's generator on its own stream - the last counter word is 1 where dp_normal has 0, so the counters
+// of the two noise streams never coincide, whatever the seeds and step / round numbers.  r is the 64-bit round counter.
+__device__ inline float cohort_dp_normal(int i, unsigned long long seed, unsigned long long r) {
+  uint32_t c[4] = {(uint32_t)i, (uint32_t)r, (uint32_t)(r >> 32), 1u};
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const float u1 = (float)((c[0] >> 8) + 1u) * 0x1p-24f, u2 = (float)(c[1] >> 8) * 0x1p-24f;
+  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+}
+
+// Diagnostic: z[i] for i < P of round r (the values cohort_dp_mean_kernel adds, without the nu factor).
+template <int NT>
+__global__ __launch_bounds__(NT) void cohort_dp_noise_kernel(float* __restrict__ z, int P, unsigned long long seed,
+                                                             unsigned long long r) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i < P) z[i] = cohort_dp_normal(i, seed, r);
+}
+
+// Clip factors of a cohort: one wave per client, scale[c] = s_c and norm[c] = n_c (reported, not read by the close).
+// Fixed summation order (per lane in column order, then a butterfly over the wave), no atomics.  Exactly P floats of a
+// client are read: the pstride - P padding floats are never written.  Thread 0 of block 0 advances the round counter
+// (dp_row_scale_kernel's pattern: its only writer; its only reader is the close launched next, which therefore draws
+// round ``round_word[0] - 1``), so a replayed graph draws fresh noise.
+constexpr int CDP_CLIENTS_PER_BLOCK = 4;
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void cohort_delta_scale_kernel(
+    const float* __restrict__ params, const float* __restrict__ global_params, int P, int M, float clip,
+    float* __restrict__ scale, float* __restrict__ norm, unsigned long long* __restrict__ round_word) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) round_word[0] = round_word[0] + 1ull;
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (c >= M) return;  // wave-uniform
+  const float* p = params + (long)c * cohort_pstride(P);
+  float ss = 0.f;
+  for (int i = lane; i < P; i += 64) {
+    const float d = p[i] - global_params[i];
+    ss += d * d;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  if (lane == 0) {
+    const float n = sqrtf(ss);
+    norm[c] = n;
+    scale[c] = n > 0.f ? fminf(1.f, clip / n) : 1.f;
+  }
+}
+
+// The close itself, one thread per parameter.  The noise is drawn before the client loads, under their latency.
+template <int NT>
+__global__ __launch_bounds__(NT) void cohort_dp_mean_kernel(
+    const float* __restrict__ params, float* __restrict__ global_params, int P, int M, float inv_M,
+    const float* __restrict__ scale, float server_lr, float noise_scale, unsigned long long seed,
+    const unsigned long long* __restrict__ round_word) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= P) return;
+  const int pstride = cohort_pstride(P);
+  float noise = 0.f;
+  if (noise_scale != 0.f) noise = noise_scale * cohort_dp_normal(i, seed, round_word[0] - 1ull);
+  const float g = global_params[i];
+  float s = scale[0] * (params[i] - g);
+  for (int c = 1; c < M; ++c) s += scale[c] * (params[(long)c * pstride + i] - g);
+  global_params[i] = g + server_lr * (s * inv_M + noise);
+}
+
 unsigned long long* g_stamps = nullptr;  // diagnostic phase stamps (ecg_tiny_set_stamps)
 
 FusedOpt no_fuse() {
@@ -1908,6 +1980,9 @@ ECG_API int ecg_tiny_cohort_wprep_stride(void) { return kCohortWprepStride; }
 // like a packed EcgTinyRound - the first step builds its operands in LDS, later steps read the images and the packed
 // rows gathered by the previous reduce - and need wprep, xg, yg and xbg, sized for M * B rows
 // (ecg_tiny_gather_floats / _halfs(L, M * B)); fp32 rounds take none of them.  There is no DP-SGD in a cohort.
+// Client-level DP (cdp_clip > 0) and a server step size other than 1 replace the mean by the DP close
+// (cohort_delta_scale_kernel + cohort_dp_mean_kernel); with the cdp_* fields and server_lr all zero the round issues the
+// launches it always issued, cohort_mean_kernel included.
 // ops/_lib.py mirrors this struct (TinyCohortRound) and checks its size against ecg_tiny_cohort_round_sizeof().
 struct EcgTinyCohortRound {
   const float* X;
@@ -1927,6 +2002,15 @@ struct EcgTinyCohortRound {
   int fanout;  // 0: the clients start from what ``params`` / ``mom`` hold (tests: distinct weights per client)
   float lr, momentum, wd;
   int nesterov, prec;
+  // Client-level DP: clip norm C of a client's round delta (0: no clipping, every factor is 1), the noise multiplier
+  // of this rank's share (noise std = cdp_sigma * cdp_clip / M per parameter; a driver of W ranks that averages their
+  // weights passes sigma / sqrt(W)), the server step size eta (0 means 1), the Philox key, the [M] clip factors and
+  // delta norms of the last round, and the 64-bit round counter (device word, advanced by every round's close).
+  float cdp_clip, cdp_sigma, server_lr;
+  unsigned long long cdp_seed;
+  float* cdp_scale;
+  float* cdp_norm;
+  unsigned long long* cdp_round;
 };
 
 ECG_API int ecg_tiny_cohort_round_sizeof(void) { return (int)sizeof(EcgTinyCohortRound); }
@@ -1963,6 +2047,16 @@ int cohort_reduce_dispatch(const float* slab, int G, int M, int stride, int P, f
 
 }  // namespace
 
+// The DP close runs in place of the mean: with a clip norm, or with a server step size other than 1 (0 means 1).
+static bool cohort_dp_on(const EcgTinyCohortRound& r) {
+  return r.cdp_clip > 0.f || (r.server_lr != 0.f && r.server_lr != 1.f);
+}
+
+// defined at the end of the file: the kernels it names are then instantiated behind cohort_mean_kernel
+static int cohort_dp_close_dispatch(const float* params, float* global_params, int P, int M, float clip, float sigma,
+                                    float server_lr, unsigned long long seed, unsigned long long* round_word,
+                                    float* scale, float* norm, hipStream_t stream);
+
 static int check_cohort_round(const EcgTinyCohortRound* r) {
   if (!r || r->steps < 1 || r->M < 1 || r->M > 65535) return ecg::kBadArg;  // (M is the grid's y extent)
   if (!r->X || !r->Y || !r->idx || !r->params || !r->slab || !r->global_params) return ecg::kBadArg;
@@ -1975,6 +2069,9 @@ static int check_cohort_round(const EcgTinyCohortRound* r) {
   // the slab and gather buffer resources hold byte sizes in 32 bits, and their row offsets are ints
   const long rows = (long)r->M * r->B;
   if (rows * r->slab_stride * 4 > INT_MAX || rows * (pack_ldb(r->L) + 8) * 4 > INT_MAX) return ecg::kTooLarge;
+  if (r->cdp_clip < 0.f || r->cdp_sigma < 0.f || r->server_lr < 0.f) return ecg::kBadArg;
+  if (r->cdp_sigma > 0.f && r->cdp_clip == 0.f) return ecg::kBadArg;
+  if (cohort_dp_on(*r) && (!r->cdp_scale || !r->cdp_norm || !r->cdp_round)) return ecg::kBadArg;
   return ecg::kOk;
 }
 
@@ -2004,6 +2101,9 @@ static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream)
                                 r.nesterov, wprep, stream, gather_next ? &ga : nullptr);
     if (st) return st;
   }
+  if (cohort_dp_on(r))
+    return cohort_dp_close_dispatch(r.params, r.global_params, P, r.M, r.cdp_clip, r.cdp_sigma, r.server_lr, r.cdp_seed,
+                                    r.cdp_round, r.cdp_scale, r.cdp_norm, stream);
   hipLaunchKernelGGL(cohort_mean_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, r.params, r.global_params,
                      P, r.M, 1.0f / (float)r.M);
   ECG_HIP_CHECK(hipGetLastError());
@@ -2021,4 +2121,48 @@ ECG_API int ecg_tiny_cohort_round_capture(void** handle, const EcgTinyCohortRoun
   const int st = check_cohort_round(round);
   if (st) return st;
   return capture_round(handle, round->steps, [&](hipStream_t cap) { return enqueue_cohort_round(*round, cap); });
+}
+
+// ---------------------------------------------------------------------------- client-level DP close
+// The two launches of the DP close (kept as two: the clip factors need every client's whole delta before any
+// parameter can be written, and a single launch would need a grid-wide barrier for nothing - the pair costs one launch
+// boundary per round).  clip == 0: no clipping (every factor is 1; the norms are still reported); server_lr == 0
+// means 1.  nu = sigma * clip / M is computed in double and rounded to fp32 here; ``sigma`` arrives as an fp32 value
+// (the caller's sigma / sqrt(W), already rounded), so nu can differ by one ulp from the value a caller rounds once
+// from doubles (train/cohort.py does): 2^-24 of the noise, far below the Box-Muller difference between device and host.
+static int cohort_dp_close_dispatch(const float* params, float* global_params, int P, int M, float clip, float sigma,
+                                    float server_lr, unsigned long long seed, unsigned long long* round_word,
+                                    float* scale, float* norm, hipStream_t stream) {
+  const float nu = (float)((double)sigma * (double)clip / (double)M);
+  hipLaunchKernelGGL(cohort_delta_scale_kernel<CDP_CLIENTS_PER_BLOCK>,
+                     dim3((M + CDP_CLIENTS_PER_BLOCK - 1) / CDP_CLIENTS_PER_BLOCK), dim3(CDP_CLIENTS_PER_BLOCK * 64), 0,
+                     stream, params, global_params, P, M, clip > 0.f ? clip : FLT_MAX, scale, norm, round_word);
+  ECG_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(cohort_dp_mean_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, params, global_params, P,
+                     M, 1.0f / (float)M, scale, server_lr == 0.f ? 1.f : server_lr, nu, seed, round_word);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+// Only the close of a cohort round, on caller-supplied buffers: ``params`` holds M clients' weights at the cohort
+// stride (ecg_tiny_cohort_param_stride(nc)), ``global`` [P] the round's starting weights and, afterwards, the new
+// ones; ``scale`` / ``norm`` [M] receive the clip factors and delta norms; the noise is that of round ``round_word[0]``
+// as found, and the word is advanced by one.  ``sigma`` is the noise multiplier of this rank's share, as
+// EcgTinyCohortRound's cdp_sigma.
+ECG_API int ecg_cohort_dp_close(const float* params, float* global, int nc, int M, float clip, float sigma,
+                                float server_lr, unsigned long long seed, unsigned long long* round_word, float* scale,
+                                float* norm, hipStream_t stream) {
+  if (!params || !global || !round_word || !scale || !norm || nc < 1 || nc > MAX_CLASSES) return ecg::kBadArg;
+  if (M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
+  if (clip < 0.f || sigma < 0.f || server_lr < 0.f || (sigma > 0.f && clip == 0.f)) return ecg::kBadArg;
+  return cohort_dp_close_dispatch(params, global, make_layout(nc).P, M, clip, sigma, server_lr, seed, round_word, scale,
+                                  norm, stream);
+}
+
+// Diagnostic: z[0:P], the standard normals the DP close draws for (seed, round r).
+ECG_API int ecg_cohort_dp_noise(float* z, int P, unsigned long long seed, unsigned long long r, hipStream_t stream) {
+  if (!z || P <= 0) return ecg::kBadArg;
+  hipLaunchKernelGGL(cohort_dp_noise_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, z, P, seed, r);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
 }

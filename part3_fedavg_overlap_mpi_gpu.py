@@ -15,6 +15,10 @@ each client's held-out last H windows)
 noise; cumulative epsilon per round, Poisson-subsampling bound; the reported training loss is not private)
 --clients-per-gpu K --cohort M --cohort-csv path (client sampling: K virtual clients per GPU, M of them drawn per
 round and trained side by side from the global weights; TinyECG on the fused or torch backend)
+--client-dp-clip C --client-dp-noise sigma --client-dp-delta delta --server-lr eta --client-privacy-csv path (client-level
+DP on a cohort round, needs --clients-per-gpu: each client's round delta clipped to l2 norm C, Gaussian noise on the
+mean, server step size eta; cumulative client-level epsilon per round at sample rate M / K, the Poisson-subsampling
+bound as an approximation; avg_loss and the evaluation metrics are not private)
 """
 from __future__ import annotations
 
