@@ -66,6 +66,13 @@ class FedAvgConfig:
     client_dp_delta: float = 1e-5
     server_lr: float = 1.0
     client_privacy_csv: str = "results/fedavg_client_privacy.csv"
+    # server optimizer on a cohort round's averaged (clipped, noised) client delta (none | sgdm | adagrad | adam | yogi;
+    # needs clients_per_gpu > 1; train/server_opt.py states the rules): momentum / first-moment and second-moment
+    # decay, and the adaptivity floor tau of adagrad, adam and yogi; server_lr is its step size
+    server_opt: str = "none"
+    server_beta1: float = 0.9
+    server_beta2: float = 0.99
+    server_tau: float = 1e-3
     results_csv: str = "results/fedavg_results.csv"
     jsonl: Optional[str] = None
     model: str = "tiny_ecg"

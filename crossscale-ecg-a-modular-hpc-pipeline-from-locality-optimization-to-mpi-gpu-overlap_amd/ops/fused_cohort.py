@@ -14,12 +14,17 @@ Client-level DP (``client_dp_clip`` > 0; DP-FedAvg) and a server step size ``ser
 l2 norm C, averaged, Gaussian noise of standard deviation ``sigma * C / (M * sqrt(world_size))`` per parameter added,
 the result applied with step size ``server_lr`` (``train/cohort.py`` states the definition).  The noise is a function
 of ``(client_dp_seed, round, parameter index)``; the round counter the kernels read is a device word this trainer owns.
+
+A server optimizer (``server_opt`` sgdm / adagrad / adam / yogi; ``train/server_opt.py`` states the rules) puts
+``cohort_server_opt_kernel`` in place of ``cohort_dp_mean_kernel``: the same averaged, clipped, noised delta, then the
+optimizer's update of its state ``server_m`` / ``server_v`` ([P] fp32 device tensors this trainer owns, kept across
+rounds, rolled back by ``prepare``, saved and restored with ``server_state`` / ``load_server_state``) and its step.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -28,7 +33,8 @@ from ..data.dataset import CohortSampler
 from ..models.tiny_ecg import TinyECG, num_params
 from .fused_tiny import _check_dataset, labels_int32, prec_id, slab_stride
 from .tiny_eval import EvalResult, TinyEvaluator, tiny_evaluate
-from ..train.cohort import check_client_dp, client_dp_seed_of, client_dp_sigma_share
+from ..train.cohort import check_client_dp, client_dp_seed_of, client_dp_sigma_share, load_server_state
+from ..train.server_opt import BETA1, BETA2, TAU, check_server_opt, server_opt_init
 
 
 class FusedCohortTrainer:
@@ -40,11 +46,13 @@ class FusedCohortTrainer:
                  momentum: float = 0.9, weight_decay: float = 0.0, nesterov: bool = False, seed: Optional[int] = None,
                  use_graph: Optional[bool] = None, precision: str = "bf16", dp_clip: float = 0.0,
                  client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
-                 server_lr: float = 1.0, world_size: int = 1):
+                 server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
+                 server_beta2: float = BETA2, server_tau: float = TAU):
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients: the cohort "
                              "reduce has no per-sample clip")
         check_client_dp(client_dp_clip, client_dp_noise, server_lr, world_size)
+        self.server_opt_id = check_server_opt(server_opt, server_beta1, server_beta2, server_tau)
         self.device = x_gpu.device
         self.precision = precision
         self.prec = prec_id(precision)
@@ -98,7 +106,10 @@ class FusedCohortTrainer:
         # the close draws its noise from (a device word: kernel arguments are baked into a captured graph)
         self.cdp_clip, self.cdp_noise, self.server_lr = float(client_dp_clip), float(client_dp_noise), float(server_lr)
         self.cdp_seed = client_dp_seed_of(seed, client_dp_seed)
-        self.client_dp = self.cdp_clip > 0.0 or self.server_lr != 1.0
+        self.server_opt = server_opt
+        self.server_beta1, self.server_beta2, self.server_tau = float(server_beta1), float(server_beta2), float(server_tau)
+        self.server_m, self.server_v = server_opt_init(server_opt, self.P, self.server_tau, self.device)
+        self.client_dp = self.cdp_clip > 0.0 or self.server_lr != 1.0 or server_opt != "none"
         self.cdp_scale = self.cdp_norm = self.cdp_round = None
         if self.client_dp:
             self.cdp_scale = torch.ones(self.M, **f32)
@@ -115,6 +126,10 @@ class FusedCohortTrainer:
             r.cdp_clip, r.cdp_sigma = self.cdp_clip, client_dp_sigma_share(self.cdp_noise, world_size)
             r.server_lr, r.cdp_seed = self.server_lr, self.cdp_seed
             r.cdp_scale, r.cdp_norm, r.cdp_round = (t.data_ptr() for t in (self.cdp_scale, self.cdp_norm, self.cdp_round))
+        if self.server_opt_id:
+            r = self._round
+            r.server_opt, r.server_beta1, r.server_beta2 = self.server_opt_id, self.server_beta1, self.server_beta2
+            r.server_tau, r.server_m, r.server_v = self.server_tau, _lib.ptr(self.server_m), _lib.ptr(self.server_v)
 
     # ------------------------------------------------------------------ graph management
     def _round_of(self, n: int, table: torch.Tensor):
@@ -149,7 +164,8 @@ class FusedCohortTrainer:
     def prepare(self, sizes) -> None:
         """Capture, upload and warm every round graph whose step count is in ``sizes`` (on both index tables).  The
         warm-up replays are rolled back: global weights, loss words, tables and the round counter - the device word of
-        the DP close with it - stay as found (the per-client buffers are scratch that every round's fan-out rewrites)."""
+        the DP close and the server optimizer's m / v with it - stay as found (the per-client buffers are scratch that
+        every round's fan-out rewrites)."""
         if not self.use_graph:
             return
         lib = _lib.kernels()
@@ -157,6 +173,7 @@ class FusedCohortTrainer:
         state = (self.params, self.loss_acc, self.idx_stage, self.idx_table)
         if self.client_dp:
             state += (self.cdp_round, self.cdp_scale, self.cdp_norm)
+        state += tuple(t for t in (self.server_m, self.server_v) if t is not None)
         snap = [t.clone() for t in state]
         stream = _lib.stream_ptr(self.device)
         for n in sizes:
@@ -182,6 +199,17 @@ class FusedCohortTrainer:
         self.cohort_round = int(r)
         if self.cdp_round is not None:
             self.cdp_round.fill_(int(r))
+
+    def server_state(self) -> Dict[str, torch.Tensor]:
+        """The server optimizer's state (copies on the CPU): ``server_m`` and, for the adaptive rules, ``server_v``;
+        synchronises."""
+        return {k: t.detach().cpu().clone() for k, t in (("server_m", self.server_m), ("server_v", self.server_v))
+                if t is not None}
+
+    def load_server_state(self, st: Dict[str, torch.Tensor]) -> None:
+        """Continue the server optimizer from ``st`` (``server_state``'s keys; checkpoint resume).  The state tensors
+        are written in place: captured graphs hold their addresses."""
+        load_server_state(self, st)
 
     def last_clip_stats(self) -> Tuple[List[float], float]:
         """(the last round's delta norms in cohort order, the share of its clients that were clipped); synchronises."""

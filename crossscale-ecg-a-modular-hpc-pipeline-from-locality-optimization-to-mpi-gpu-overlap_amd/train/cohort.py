@@ -16,12 +16,16 @@ in fp32, ``nu = fp32(sigma * C / (M * sqrt(W)))`` with sigma = ``client_dp_noise
 averages W ranks' weights, which leaves noise of standard deviation sigma * C / (M * W) on a mean of sensitivity
 C / (M * W)), and ``z = philox.normal(client_dp_seed, round, P, stream=1)``: the definition that
 ``cohort_dp_mean_kernel`` of csrc/kernels/tiny_ecg_step.hip implements.
+
+A server optimizer (``server_opt`` sgdm / adagrad / adam / yogi; ``train/server_opt.py`` states the rules) takes the
+bracket above - Delta, the averaged, clipped, noised delta - as its pseudo-gradient in place of the plain step
+``g + eta * Delta``; its state ``server_m`` / ``server_v`` lives across rounds (``server_state`` / ``load_server_state``).
 """
 from __future__ import annotations
 
 import copy
 import math
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -29,6 +33,7 @@ import torch.nn.functional as F
 
 from ..data.dataset import CohortSampler
 from ..utils import philox
+from .server_opt import BETA1, BETA2, TAU, check_server_opt, server_opt_init, server_opt_step
 
 
 class TorchCohortTrainer:
@@ -37,10 +42,12 @@ class TorchCohortTrainer:
                  momentum: float = 0.9, weight_decay: float = 0.0, nesterov: bool = False,
                  amp_dtype: Optional[torch.dtype] = None, seed: Optional[int] = None, dp_clip: float = 0.0,
                  client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
-                 server_lr: float = 1.0, world_size: int = 1):
+                 server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
+                 server_beta2: float = BETA2, server_tau: float = TAU):
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients")
         check_client_dp(client_dp_clip, client_dp_noise, server_lr, world_size)
+        check_server_opt(server_opt, server_beta1, server_beta2, server_tau)
         self.model, self.x, self.y = model, x, y
         self.device = x.device
         self.B, self.S, self.K = int(batch_size), int(steps_per_round), int(clients)
@@ -61,12 +68,24 @@ class TorchCohortTrainer:
         self.cdp_clip, self.cdp_noise, self.server_lr = float(client_dp_clip), float(client_dp_noise), float(server_lr)
         self.cdp_seed = client_dp_seed_of(seed, client_dp_seed)
         self.cdp_nu = client_dp_nu(self.cdp_noise, self.cdp_clip, self.M, world_size)
-        self.client_dp = self.cdp_clip > 0.0 or self.server_lr != 1.0
+        self.server_opt = server_opt
+        self.server_beta1, self.server_beta2, self.server_tau = float(server_beta1), float(server_beta2), float(server_tau)
+        self.server_m, self.server_v = server_opt_init(server_opt, sum(p.numel() for p in model.parameters()),
+                                                       self.server_tau, self.device)
+        self.client_dp = self.cdp_clip > 0.0 or self.server_lr != 1.0 or server_opt != "none"
         self._norms: List[float] = []
         self._scales: List[float] = []
 
     def set_cohort_round(self, r: int) -> None:
         self.cohort_round = int(r)
+
+    def server_state(self) -> Dict[str, torch.Tensor]:
+        """The server optimizer's state (copies on the CPU): ``server_m`` and, for the adaptive rules, ``server_v``."""
+        return {k: t.detach().cpu().clone() for k, t in (("server_m", self.server_m), ("server_v", self.server_v))
+                if t is not None}
+
+    def load_server_state(self, st: Dict[str, torch.Tensor]) -> None:
+        load_server_state(self, st)
 
     def _client_round(self, j: int, n: int, table: torch.Tensor) -> List[torch.Tensor]:
         """Client j of the cohort: ``n`` SGD steps from the global weights; returns its parameters (detached copies)."""
@@ -122,7 +141,12 @@ class TorchCohortTrainer:
         if self.cdp_nu != 0.0:
             z = philox.normal(self.cdp_seed, r, g.numel(), stream=1).astype(np.float32)
             upd = upd + torch.tensor(self.cdp_nu, **f32) * torch.from_numpy(z).to(self.device)
-        new = g + torch.tensor(self.server_lr, **f32) * upd
+        if self.server_opt == "none":
+            new = g + torch.tensor(self.server_lr, **f32) * upd
+        else:
+            new, self.server_m, self.server_v = server_opt_step(
+                self.server_opt, g, upd, self.server_m, self.server_v, self.server_lr, self.server_beta1,
+                self.server_beta2, self.server_tau)
         off = 0
         with torch.no_grad():
             for pg in self.model.parameters():
@@ -151,6 +175,17 @@ class TorchCohortTrainer:
 
     def avg_loss(self) -> float:
         return float(self.loss_acc.item()) / (self.M * max(1, self._loss_steps))
+
+
+def load_server_state(trainer, st: Dict[str, torch.Tensor]) -> None:
+    """Copy ``server_m`` / ``server_v`` of ``st`` into a cohort trainer's state tensors (those it has)."""
+    for key in ("server_m", "server_v"):
+        t = getattr(trainer, key, None)
+        if t is None or st.get(key) is None:
+            continue
+        if st[key].shape != t.shape:
+            raise ValueError(f"{key} shape {tuple(st[key].shape)} != {tuple(t.shape)}")
+        t.copy_(st[key].to(t.device))
 
 
 def check_client_dp(clip: float, noise: float, server_lr: float, world_size: int) -> None:

@@ -50,6 +50,14 @@ MI355X execution (vs the reference's host-staged per-tensor MPI calls and per-st
     epsilon per round (``utils.privacy`` at ``sample_rate = M / K``, one composition per round: the Poisson-subsampling
     bound applied to fixed-size sampling without replacement - an approximation, as for DP-SGD) with rank 0's median
     client norm and clipped share to ``--client-privacy-csv``.  ``avg_loss`` and the evaluation metrics are not private.
+  * ``--server-opt {none,sgdm,adagrad,adam,yogi}`` / ``--server-beta1`` / ``--server-beta2`` / ``--server-tau``: a server
+    optimizer (FedOpt) on a cohort round's averaged, clipped, noised client delta, with step size ``--server-lr`` (needs
+    ``--clients-per-gpu``; ``train/server_opt.py`` states the rules).  Its state m / v is per rank, lives across rounds
+    and is part of the per-rank checkpoint, so ``--resume`` continues it.  sgdm is linear in the delta: under ``--sync
+    fedavg`` every rank keeps its own m and the unchanged all-reduce(AVG) of ``g + eta * m_rank`` is the global FedAvgM
+    step with ``m = AVG(m_rank)``.  adagrad, adam and yogi are nonlinear in the delta and are rejected under ``--sync
+    fedavg`` on more than one rank (they would have to follow an all-reduce of the deltas); they run on one rank and
+    under ``--sync none``.
 """
 from __future__ import annotations
 
@@ -76,6 +84,7 @@ from ..utils.ckpt import (ckpt_path, save_checkpoint, load_checkpoint, latest_ch
 from ..utils.csvio import (RoundStats, append_results, ROUND_COLUMNS, EVAL_COLUMNS, PRIVACY_COLUMNS,
                            COHORT_COLUMNS, CLIENT_PRIVACY_COLUMNS)
 from ..utils.philox import mix64
+from .server_opt import ADAPTIVE as ADAPTIVE_SERVER_OPTS, check_server_opt
 from ..utils.privacy import epsilon as dp_epsilon
 from ..utils.log import RankLogger
 from .local import TorchLocalTrainer
@@ -231,6 +240,25 @@ def check_client_dp_config(cfg: FedAvgConfig) -> None:
         raise ValueError("--client-dp-delta must be in (0, 1)")
 
 
+def check_server_opt_config(cfg: FedAvgConfig, ctx: DistContext) -> None:
+    """A server optimizer acts on a cohort round's averaged client delta: it needs client sampling (and with it
+    everything ``check_cohort_config`` asks for).  Under ``--sync fedavg`` on W > 1 ranks only sgdm is exact: its rule
+    is linear in Delta, so the all-reduce(AVG) of the ranks' ``g + eta * m_rank`` is the global FedAvgM step with
+    ``m = AVG(m_rank)``; the adaptive rules are nonlinear in Delta and would have to follow the all-reduce."""
+    check_server_opt(cfg.server_opt, cfg.server_beta1, cfg.server_beta2, cfg.server_tau)
+    if cfg.server_opt == "none":
+        return
+    if cfg.clients_per_gpu <= 1:
+        raise ValueError("--server-opt / --server-beta1 / --server-beta2 / --server-tau need client sampling "
+                         "(--clients-per-gpu K > 1): the server optimizer steps on the mean of a cohort's client deltas")
+    if cfg.server_opt in ADAPTIVE_SERVER_OPTS and cfg.sync == "fedavg" and ctx.distributed and ctx.world_size > 1:
+        raise ValueError(f"--server-opt {cfg.server_opt} does not support --sync fedavg on more than one rank: its step "
+                         "m / (sqrt(v) + tau) is nonlinear in the averaged delta, so it must follow the all-reduce of "
+                         "the ranks' deltas, and the driver all-reduces the weights after each rank's own step (the "
+                         "next item: all-reduce the deltas, then step); use --server-opt sgdm, whose rule is linear, "
+                         "one rank, or --sync none")
+
+
 def client_dp_world(cfg: FedAvgConfig, ctx: DistContext) -> int:
     """The number of ranks whose weights the driver averages after a round: every rank adds sigma / sqrt(that) of the
     client-level noise.  Only ``--sync fedavg`` on more than one rank averages; an independent client (``--sync none``, a
@@ -243,10 +271,12 @@ def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistCont
     check_dp_config(cfg, config_name, backend)
     check_cohort_config(cfg, backend)
     check_client_dp_config(cfg)
+    check_server_opt_config(cfg, ctx)
     if cfg.clients_per_gpu > 1:
         kw = dict(clients=cfg.clients_per_gpu, cohort=cohort_size(cfg), lr=cfg.lr, momentum=cfg.momentum, seed=seed,
                   client_dp_clip=cfg.client_dp_clip, client_dp_noise=cfg.client_dp_noise, client_dp_seed=mix64(seed),
-                  server_lr=cfg.server_lr, world_size=client_dp_world(cfg, ctx))
+                  server_lr=cfg.server_lr, world_size=client_dp_world(cfg, ctx), server_opt=cfg.server_opt,
+                  server_beta1=cfg.server_beta1, server_beta2=cfg.server_beta2, server_tau=cfg.server_tau)
         if backend == "fused":
             from ..ops.fused_cohort import FusedCohortTrainer
             prec = "bf16" if (config_name == "G1" and cfg.amp_dtype == "bf16") else "fp32"
@@ -375,6 +405,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         check_dp_config(cfg, cname, pick_backend(cfg, cname, ctx))
         check_cohort_config(cfg, pick_backend(cfg, cname, ctx))
     check_client_dp_config(cfg)
+    check_server_opt_config(cfg, ctx)
     M = cohort_size(cfg)  # clients trained per GPU and round (1: no client sampling)
     all_rows: List[Dict] = []
     fcomm = FedAvgComm(ctx)
@@ -387,6 +418,9 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
             model.flatten_parameters()
         trainer = make_trainer(cfg, cname, model, x, y, ctx, backend)
         log.info(f"[fedavg] {cname}: kernel backend {backend}")
+        if cfg.server_opt != "none":
+            log.event("server_opt", config=cname, server_opt=cfg.server_opt, server_lr=cfg.server_lr,
+                      beta1=cfg.server_beta1, beta2=cfg.server_beta2, tau=cfg.server_tau)
         start_round = _resume(cfg, cname, ctx, comm, model, trainer, log) if cfg.resume else 0
         if hasattr(trainer, "set_cohort_round"):  # the cohort sampler is a function of (seed, round): no other state
             trainer.set_cohort_round(start_round)

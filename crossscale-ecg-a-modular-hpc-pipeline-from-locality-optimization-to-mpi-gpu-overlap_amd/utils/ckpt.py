@@ -7,7 +7,7 @@ Layout (plain ``torch.save``, loaded with ``weights_only=True`` - no pickle exec
   its ``"model"`` entry anywhere.
 * ``checkpoints/fedavg_{cfg}_round{r:05d}.rank{k}.pt`` - written by EVERY rank into its own ``ckpt_dir``: the
   client-local state FedAvg never averages (SGD momentum, the batch sampler's generator / epoch block / cursor,
-  the CPU RNG, a cohort trainer's round counter ``cohort_round``, the DP-SGD step counter ``dp_steps`` - a resumed run continues its noise stream, it does not replay it) and, for ``--sync none`` (independent clients), the client's own flat weights.
+  the CPU RNG, a cohort trainer's round counter ``cohort_round`` and its server optimizer's ``server_m`` / ``server_v`` (a resumed run continues the optimizer, it does not restart it), the DP-SGD step counter ``dp_steps`` - a resumed run continues its noise stream, it does not replay it) and, for ``--sync none`` (independent clients), the client's own flat weights.
 * ``--overlap delayed``: a checkpoint of round r holds avg_r (the all-reduce of round r's weights, waited for on
   the device); the run itself keeps its one-round-stale correction pending, so its trajectory does not depend
   on ``--ckpt-every``.  A resume starts from avg_r with nothing in flight: resuming ends the staleness once.
@@ -75,6 +75,8 @@ def trainer_local_state(trainer) -> Dict[str, Any]:
         st["dp_steps"] = int(trainer.dp_steps)
     if getattr(trainer, "cohort_round", None) is not None:  # cohort trainers: the sampler is a function of it
         st["cohort_round"] = int(trainer.cohort_round)
+    if hasattr(trainer, "server_state"):  # cohort trainers with a server optimizer: its m (and v), server state
+        st.update(trainer.server_state())
     return st
 
 
@@ -97,6 +99,8 @@ def load_trainer_local_state(trainer, st: Dict[str, Any]) -> None:
         trainer.set_dp_steps(int(st["dp_steps"]))
     if st.get("cohort_round") is not None and hasattr(trainer, "set_cohort_round"):
         trainer.set_cohort_round(int(st["cohort_round"]))
+    if hasattr(trainer, "load_server_state"):
+        trainer.load_server_state(st)
     if st.get("rng_cpu") is not None:
         torch.set_rng_state(st["rng_cpu"])
 

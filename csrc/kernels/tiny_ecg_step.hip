@@ -1982,7 +1982,8 @@ ECG_API int ecg_tiny_cohort_wprep_stride(void) { return kCohortWprepStride; }
 // (ecg_tiny_gather_floats / _halfs(L, M * B)); fp32 rounds take none of them.  There is no DP-SGD in a cohort.
 // Client-level DP (cdp_clip > 0) and a server step size other than 1 replace the mean by the DP close
 // (cohort_delta_scale_kernel + cohort_dp_mean_kernel); with the cdp_* fields and server_lr all zero the round issues the
-// launches it always issued, cohort_mean_kernel included.
+// launches it always issued, cohort_mean_kernel included.  A server optimizer (server_opt != 0) closes the round with
+// cohort_delta_scale_kernel + cohort_server_opt_kernel; with server_opt == 0 the close is the one it was.
 // ops/_lib.py mirrors this struct (TinyCohortRound) and checks its size against ecg_tiny_cohort_round_sizeof().
 struct EcgTinyCohortRound {
   const float* X;
@@ -2011,6 +2012,14 @@ struct EcgTinyCohortRound {
   float* cdp_scale;
   float* cdp_norm;
   unsigned long long* cdp_round;
+  // Server optimizer on the averaged (clipped, noised) client delta: 0 none (the plain server step), 1 sgdm (FedAvgM),
+  // 2 adagrad, 3 adam, 4 yogi (cohort_server_opt_kernel states the rules); beta1, beta2 in [0, 1), tau > 0 (2..4), and
+  // the server state m / v [P] (fp32, read and written by every round's close; v may be null for sgdm).  With
+  // server_opt == 0 the other five fields are not read.
+  int server_opt;
+  float server_beta1, server_beta2, server_tau;
+  float* server_m;
+  float* server_v;
 };
 
 ECG_API int ecg_tiny_cohort_round_sizeof(void) { return (int)sizeof(EcgTinyCohortRound); }
@@ -2049,13 +2058,21 @@ int cohort_reduce_dispatch(const float* slab, int G, int M, int stride, int P, f
 
 // The DP close runs in place of the mean: with a clip norm, or with a server step size other than 1 (0 means 1).
 static bool cohort_dp_on(const EcgTinyCohortRound& r) {
-  return r.cdp_clip > 0.f || (r.server_lr != 0.f && r.server_lr != 1.f);
+  return r.cdp_clip > 0.f || (r.server_lr != 0.f && r.server_lr != 1.f) || r.server_opt != 0;
 }
 
 // defined at the end of the file: the kernels it names are then instantiated behind cohort_mean_kernel
 static int cohort_dp_close_dispatch(const float* params, float* global_params, int P, int M, float clip, float sigma,
                                     float server_lr, unsigned long long seed, unsigned long long* round_word,
                                     float* scale, float* norm, hipStream_t stream);
+
+// A server optimizer (server_opt != 0) closes the round with cohort_server_opt_kernel in place of cohort_dp_mean_kernel;
+// both defined at the end of the file, like the DP close.
+static int check_server_opt(int opt, float b1, float b2, float tau, const float* m, const float* v);
+static int cohort_server_close_dispatch(const float* params, float* global_params, int P, int M, float clip,
+                                        float sigma, float server_lr, unsigned long long seed,
+                                        unsigned long long* round_word, float* scale, float* norm, int opt, float b1,
+                                        float b2, float tau, float* m, float* v, hipStream_t stream);
 
 static int check_cohort_round(const EcgTinyCohortRound* r) {
   if (!r || r->steps < 1 || r->M < 1 || r->M > 65535) return ecg::kBadArg;  // (M is the grid's y extent)
@@ -2072,6 +2089,8 @@ static int check_cohort_round(const EcgTinyCohortRound* r) {
   if (r->cdp_clip < 0.f || r->cdp_sigma < 0.f || r->server_lr < 0.f) return ecg::kBadArg;
   if (r->cdp_sigma > 0.f && r->cdp_clip == 0.f) return ecg::kBadArg;
   if (cohort_dp_on(*r) && (!r->cdp_scale || !r->cdp_norm || !r->cdp_round)) return ecg::kBadArg;
+  if (r->server_opt != 0)
+    return check_server_opt(r->server_opt, r->server_beta1, r->server_beta2, r->server_tau, r->server_m, r->server_v);
   return ecg::kOk;
 }
 
@@ -2101,6 +2120,10 @@ static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream)
                                 r.nesterov, wprep, stream, gather_next ? &ga : nullptr);
     if (st) return st;
   }
+  if (r.server_opt != 0)
+    return cohort_server_close_dispatch(r.params, r.global_params, P, r.M, r.cdp_clip, r.cdp_sigma, r.server_lr,
+                                        r.cdp_seed, r.cdp_round, r.cdp_scale, r.cdp_norm, r.server_opt, r.server_beta1,
+                                        r.server_beta2, r.server_tau, r.server_m, r.server_v, stream);
   if (cohort_dp_on(r))
     return cohort_dp_close_dispatch(r.params, r.global_params, P, r.M, r.cdp_clip, r.cdp_sigma, r.server_lr, r.cdp_seed,
                                     r.cdp_round, r.cdp_scale, r.cdp_norm, stream);
@@ -2165,4 +2188,118 @@ ECG_API int ecg_cohort_dp_noise(float* z, int P, unsigned long long seed, unsign
   hipLaunchKernelGGL(cohort_dp_noise_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, z, P, seed, r);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
+}
+
+// ---------------------------------------------------------------------------- server optimizers (FedOpt close)
+// The close of a cohort round with a server optimizer (Reddi et al., "Adaptive Federated Optimization"), in place of
+// cohort_dp_mean_kernel: Delta_i is formed exactly as there - the clipped client deltas in ascending order times
+// inv_M, plus nu * z_i drawn on stream word 1 for round ``round_word[0] - 1`` - and then, with the server state m, v
+// [P] (fp32, kept across rounds; no bias correction, as in the paper) and one_minus = 1 - beta in fp32,
+//   OPT 1 sgdm (FedAvgM):  m = b1 m + Delta;               g += eta m
+//   OPT 2 adagrad:         m = b1 m + (1 - b1) Delta;      v = v + Delta^2
+//   OPT 3 adam:            m as adagrad;                   v = b2 v + (1 - b2) Delta^2
+//   OPT 4 yogi:            m as adagrad;                   v = v - (1 - b2) Delta^2 sign(v - Delta^2), sign(0) = 0
+//   OPT 2..4:              g += eta m / (sqrt(v) + tau)    (the new m and v; division and sqrt correctly rounded)
+// One thread per parameter reads g[i], m[i], v[i] and the M client values and writes g[i], m[i] and (OPT 2..4) v[i]:
+// no atomics, a fixed order.  sgdm takes v == nullptr.  With b1 == 0 and m == 0 sgdm is cohort_dp_mean_kernel's result
+// bit for bit (m = Delta, g + eta * Delta).  (Defined and first named here, behind every older kernel.)
+namespace {
+
+constexpr int SOPT_SGDM = 1, SOPT_ADAGRAD = 2, SOPT_ADAM = 3, SOPT_YOGI = 4;
+
+template <int NT, int OPT>
+__global__ __launch_bounds__(NT) void cohort_server_opt_kernel(
+    const float* __restrict__ params, float* __restrict__ global_params, int P, int M, float inv_M,
+    const float* __restrict__ scale, float server_lr, float noise_scale, unsigned long long seed,
+    const unsigned long long* __restrict__ round_word, float b1, float b2, float tau, float* __restrict__ m,
+    float* __restrict__ v) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= P) return;
+  const int pstride = cohort_pstride(P);
+  float noise = 0.f;
+  if (noise_scale != 0.f) noise = noise_scale * cohort_dp_normal(i, seed, round_word[0] - 1ull);
+  const float g = global_params[i];
+  const float m0 = m[i];
+  float v1 = 0.f;
+  if (OPT != SOPT_SGDM) v1 = v[i];
+  // The fused multiply-adds of Delta and of the sgdm step are written out: they are what cohort_dp_mean_kernel's
+  // expressions contract to, and left to the compiler b1 * m0 and s * inv_M pair up in one packed multiply, which
+  // rounds Delta once more than that kernel does.
+  float s = scale[0] * (params[i] - g);
+  for (int c = 1; c < M; ++c) s = __builtin_fmaf(scale[c], params[(long)c * pstride + i] - g, s);
+  const float delta = __builtin_fmaf(s, inv_M, noise);
+  float m1;
+  if (OPT == SOPT_SGDM) {
+    m1 = __builtin_fmaf(b1, m0, delta);
+    global_params[i] = __builtin_fmaf(server_lr, m1, g);
+  } else {
+    m1 = b1 * m0 + (1.f - b1) * delta;
+    const float d2 = delta * delta;
+    if (OPT == SOPT_ADAGRAD) {
+      v1 = v1 + d2;
+    } else if (OPT == SOPT_ADAM) {
+      v1 = b2 * v1 + (1.f - b2) * d2;
+    } else {
+      const float e = v1 - d2;
+      const float sg = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
+      v1 = v1 - (1.f - b2) * d2 * sg;
+    }
+    v[i] = v1;
+    global_params[i] = g + (server_lr * m1) / (sqrtf(v1) + tau);
+  }
+  m[i] = m1;
+}
+
+}  // namespace
+
+static int check_server_opt(int opt, float b1, float b2, float tau, const float* m, const float* v) {
+  if (opt < SOPT_SGDM || opt > SOPT_YOGI || !m) return ecg::kBadArg;
+  if (!(b1 >= 0.f && b1 < 1.f) || !(b2 >= 0.f && b2 < 1.f)) return ecg::kBadArg;
+  if (opt != SOPT_SGDM && (!v || !(tau > 0.f))) return ecg::kBadArg;
+  return ecg::kOk;
+}
+
+// The two launches of the close with a server optimizer: cohort_delta_scale_kernel as in the DP close (it advances the
+// round word and reports the norms), then cohort_server_opt_kernel in place of cohort_dp_mean_kernel - two launches for
+// the reason given at cohort_dp_close_dispatch.  clip, sigma, server_lr and nu as there.
+static int cohort_server_close_dispatch(const float* params, float* global_params, int P, int M, float clip,
+                                        float sigma, float server_lr, unsigned long long seed,
+                                        unsigned long long* round_word, float* scale, float* norm, int opt, float b1,
+                                        float b2, float tau, float* m, float* v, hipStream_t stream) {
+  const int st = check_server_opt(opt, b1, b2, tau, m, v);
+  if (st) return st;
+  const float nu = (float)((double)sigma * (double)clip / (double)M);
+  const float eta = server_lr == 0.f ? 1.f : server_lr, inv_M = 1.0f / (float)M;
+  hipLaunchKernelGGL(cohort_delta_scale_kernel<CDP_CLIENTS_PER_BLOCK>,
+                     dim3((M + CDP_CLIENTS_PER_BLOCK - 1) / CDP_CLIENTS_PER_BLOCK), dim3(CDP_CLIENTS_PER_BLOCK * 64), 0,
+                     stream, params, global_params, P, M, clip > 0.f ? clip : FLT_MAX, scale, norm, round_word);
+  ECG_HIP_CHECK(hipGetLastError());
+  const dim3 grid((P + 255) / 256), block(256);
+  const unsigned long long* word = round_word;
+#define ECG_SERVER_OPT_LAUNCH(OPT)                                                                                   \
+  hipLaunchKernelGGL((cohort_server_opt_kernel<256, OPT>), grid, block, 0, stream, params, global_params, P, M, inv_M, \
+                     (const float*)scale, eta, nu, seed, word, b1, b2, tau, m, v)
+  switch (opt) {
+    case SOPT_SGDM: ECG_SERVER_OPT_LAUNCH(SOPT_SGDM); break;
+    case SOPT_ADAGRAD: ECG_SERVER_OPT_LAUNCH(SOPT_ADAGRAD); break;
+    case SOPT_ADAM: ECG_SERVER_OPT_LAUNCH(SOPT_ADAM); break;
+    default: ECG_SERVER_OPT_LAUNCH(SOPT_YOGI); break;
+  }
+#undef ECG_SERVER_OPT_LAUNCH
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+// ecg_cohort_dp_close's twin with a server optimizer: the same buffers and meaning of clip, sigma, server_lr, seed and
+// the round word, plus ``opt`` (1 sgdm, 2 adagrad, 3 adam, 4 yogi), beta1, beta2 in [0, 1), tau > 0 (opt 2..4) and the
+// server state ``m`` / ``v`` [P], read and written (``v`` may be null for sgdm).
+ECG_API int ecg_cohort_server_close(const float* params, float* global, int nc, int M, float clip, float sigma,
+                                    float server_lr, unsigned long long seed, unsigned long long* round_word,
+                                    float* scale, float* norm, int opt, float b1, float b2, float tau, float* m,
+                                    float* v, hipStream_t stream) {
+  if (!params || !global || !round_word || !scale || !norm || nc < 1 || nc > MAX_CLASSES) return ecg::kBadArg;
+  if (M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
+  if (clip < 0.f || sigma < 0.f || server_lr < 0.f || (sigma > 0.f && clip == 0.f)) return ecg::kBadArg;
+  return cohort_server_close_dispatch(params, global, make_layout(nc).P, M, clip, sigma, server_lr, seed, round_word,
+                                      scale, norm, opt, b1, b2, tau, m, v, stream);
 }

@@ -19,6 +19,9 @@ round and trained side by side from the global weights; TinyECG on the fused or 
 DP on a cohort round, needs --clients-per-gpu: each client's round delta clipped to l2 norm C, Gaussian noise on the
 mean, server step size eta; cumulative client-level epsilon per round at sample rate M / K, the Poisson-subsampling
 bound as an approximation; avg_loss and the evaluation metrics are not private)
+--server-opt {none,sgdm,adagrad,adam,yogi} --server-beta1 b1 --server-beta2 b2 --server-tau tau (server optimizer on a
+cohort round's averaged client delta with step size --server-lr, needs --clients-per-gpu: FedAvgM, FedAdagrad, FedAdam,
+FedYogi; state kept in the per-rank checkpoint; the three adaptive ones not under --sync fedavg on more than one rank)
 """
 from __future__ import annotations
 
