@@ -67,7 +67,10 @@ class TinyRound(C.Structure):
                 ("L", i32), ("nc", i32), ("slab_stride", i32), ("B", i32), ("steps", i32),
                 ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32),
                 ("dp_clip", f32), ("dp_sigma", f32), ("dp_seed", u64), ("dp_scale", vp), ("dp_step", vp),
-                ("xbg", vp)]
+                ("xbg", vp), ("xpk", vp), ("prepack", i32)]
+
+
+PREPACK = {"none": 0, "gather": 1, "direct": 2}  # kPrepack* of csrc/kernels/tiny_ecg_step.hip (TinyRound.prepack)
 
 
 class TinyCohortRound(C.Structure):
@@ -115,6 +118,8 @@ def _bind_kernels(lib: C.CDLL) -> None:
     _sig(lib, "ecg_tiny_cohort_wprep_stride", [])
     _sig(lib, "ecg_tiny_gather_floats", [i32, i32], i64)
     _sig(lib, "ecg_tiny_gather_halfs", [i32, i32], i64)
+    _sig(lib, "ecg_tiny_pack_halfs", [i32, i64], i64)
+    _sig(lib, "ecg_tiny_pack_dataset", [vp, i64, i64, i32, vp, vp])
     _sig(lib, "ecg_tiny_step_grads_twice", [vp, i32, i64, vp, vp, vp, i32, vp, i32, i32, f32, i32, vp, vp])
     _sig(lib, "ecg_tiny_force_waves", [i32])
     _sig(lib, "ecg_tiny_set_stamps", [vp])

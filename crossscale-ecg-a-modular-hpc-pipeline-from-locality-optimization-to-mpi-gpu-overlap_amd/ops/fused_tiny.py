@@ -117,6 +117,47 @@ def tiny_step_grads(flat_params: torch.Tensor, x: torch.Tensor, y32: torch.Tenso
     return slab
 
 
+# ``FusedTinyTrainer(prepack=...)``: what a round does with the dataset packed once (TinyRound.prepack).  The default
+# is set by measurement (profiles/r15/tiny_prepacked.txt: 9.76-9.81 us/step unpacked, 9.58-9.64 gather, 9.45-9.52
+# direct); ECG_TINY_PREPACK=none|gather|direct overrides it for a process (A/B runs of an unchanged driver), an
+# explicit argument overrides both.  A caller that sets ``gather=`` or ``pack=`` itself asks for that gather-based
+# round and its buffers, so the default then is "none".
+PREPACK_DEFAULT = "direct"
+# Largest share of the device's free memory the packed shard may take (it is about 0.52 of the fp32 shard at L = 500);
+# above it the trainer keeps the unpacked path.  A quarter leaves the 64 GB resident runs (33 GB packed, 288 GB HBM)
+# their packed copy and refuses it where the shard itself already fills half of what is free.
+PREPACK_SHARE = 0.25
+
+
+def _prepack_variant(prepack, explicit_gather: bool = False) -> str:
+    if prepack is None:
+        prepack = "none" if explicit_gather else os.environ.get("ECG_TINY_PREPACK") or PREPACK_DEFAULT
+    if prepack is True:
+        prepack = "gather" if PREPACK_DEFAULT == "none" else PREPACK_DEFAULT  # (the cheaper form if none is default)
+    if prepack is False:
+        prepack = "none"
+    if prepack not in _lib.PREPACK:
+        raise ValueError(f"prepack must be a bool or one of {list(_lib.PREPACK)}, got {prepack!r}")
+    return prepack
+
+
+def pack_dataset(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The windows ``x`` [N, L] as packed bf16 rows [N, ldb]: 4 zeros, bf16(x[n]), zeros up to ldb = L rounded up to
+    32, plus 8 - the rows the packed step kernel reads (csrc/kernels/tiny_ecg_step.hip kPackLead).  Every element of
+    ``out``, pads included, is written."""
+    _check_dataset(x, None, 0)
+    lib = _lib.kernels()
+    N, L = x.shape
+    ldb = lib.ecg_tiny_pack_halfs(L, 1)
+    if out is None:
+        out = torch.empty((N, ldb), dtype=torch.bfloat16, device=x.device)
+    if out.shape != (N, ldb) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"packed rows must be a contiguous bfloat16 [{N}, {ldb}] tensor on the dataset's device")
+    _lib.check(lib.ecg_tiny_pack_dataset(x.data_ptr(), x.stride(0), N, L, out.data_ptr(), _lib.stream_ptr(x.device)),
+               "ecg_tiny_pack_dataset")
+    return out
+
+
 def check_dp_args(dp_clip: float, dp_noise: float) -> None:
     if not dp_clip >= 0.0 or not dp_noise >= 0.0:
         raise ValueError(f"dp_clip and dp_noise must be >= 0, got {dp_clip} and {dp_noise}")
@@ -183,6 +224,19 @@ class FusedTinyTrainer:
     ``pack=False`` - the round exactly as it was, ``xg`` rows into the unpacked kernel - gives identical results.
     ``xg`` is written either way.
 
+    ``prepack`` (needs ``pack``): the dataset does not change for the life of a trainer, so its packed form is built
+    once, at construction (``xpk``, [N, ldb] bf16: about half the fp32 shard again), instead of being converted,
+    padded and copied as fp32 on every step.  ``"gather"``: the gather blocks copy packed rows ``xpk[idx[b]]`` into
+    ``xbg`` - 16 bytes per thread, fewer blocks, no fp32 read, no conversion, and no ``xg``, which is neither allocated
+    nor written.  ``"direct"``: no gather at all - the packed step kernel loads ``idx[b]`` itself and reads its row
+    from ``xpk`` (no ``xg`` / ``yg`` / ``xbg``); this is the fastest form measured and the default.  ``"none"`` /
+    False: the round as above.  None: ``PREPACK_DEFAULT`` (or ECG_TINY_PREPACK) - but "none" for a caller that
+    passes ``gather=`` or ``pack=``, who asks for that gather-based round and its buffers; True: the default form.
+    Results are bitwise the same in every form.  Callers that rewrite ``x`` in place call ``repack()``.  If the packed shard would take more than
+    ``prepack_share`` of the device's free memory, or its allocation fails, the trainer keeps the unpacked path:
+    ``prepack`` is then ``"none"`` and ``prepack_fallback`` says why (None otherwise).  Measurements:
+    profiles/r15/tiny_prepacked.txt.
+
     DP-SGD (``dp_clip`` > 0): every step clips each sample's gradient to l2 norm ``dp_clip`` and adds Gaussian noise
     of standard deviation ``dp_noise * dp_clip`` to their sum before the 1/B mean - two launches on the reduce side
     (clip factors, then the clipped and noised reduce + SGD), the step kernel unchanged.  The noise is Philox
@@ -194,7 +248,9 @@ class FusedTinyTrainer:
     def __init__(self, model: TinyECG, x_gpu: torch.Tensor, y_gpu: torch.Tensor, batch_size: int,
                  steps_per_round: int, lr: float = 1e-2, momentum: float = 0.9, weight_decay: float = 0.0,
                  nesterov: bool = False, seed: Optional[int] = None, use_graph: Optional[bool] = None,
-                 precision: str = "bf16", prefrag: bool = True, gather: bool = True, pack: bool = True,
+                 precision: str = "bf16", prefrag: bool = True, gather: Optional[bool] = None,
+                 pack: Optional[bool] = None,
+                 prepack=None, prepack_share: float = PREPACK_SHARE,
                  dp_clip: float = 0.0, dp_noise: float = 0.0, dp_seed: Optional[int] = None):
         self.device = x_gpu.device
         self.precision = precision
@@ -234,15 +290,22 @@ class FusedTinyTrainer:
             raise ValueError(f"window length {L} too long for the fused kernel ({smem} B LDS)")
         self.prefrag = bool(prefrag) and precision == "bf16"
         self.wprep = new_wprep(self.device) if self.prefrag else None
-        self.gather = bool(gather) and self.prefrag
-        self.xg = self.yg = None
-        if self.gather:
-            self.xg = torch.zeros(lib.ecg_tiny_gather_floats(L, self.B), dtype=torch.float32, device=self.device)
+        explicit_gather = gather is not None or pack is not None
+        self.gather = (True if gather is None else bool(gather)) and self.prefrag
+        self.pack = (True if pack is None else bool(pack)) and self.gather
+        self.prepack_share = float(prepack_share)
+        self.prepack, self.prepack_fallback = _prepack_variant(prepack, explicit_gather) if self.pack else "none", None
+        self.xpk = None
+        if self.prepack != "none":
+            self._alloc_prepacked()
+        self.xg = self.yg = self.xbg = None
+        if self.gather and self.prepack != "direct":
             self.yg = torch.zeros(2 * self.B, dtype=torch.int32, device=self.device)
-        self.pack = bool(pack) and self.gather
-        self.xbg = None
-        if self.pack:
-            self.xbg = torch.zeros(lib.ecg_tiny_gather_halfs(L, self.B), dtype=torch.bfloat16, device=self.device)
+            if self.prepack == "none":
+                self.xg = torch.zeros(lib.ecg_tiny_gather_floats(L, self.B), dtype=torch.float32, device=self.device)
+            if self.pack:
+                self.xbg = torch.zeros(lib.ecg_tiny_gather_halfs(L, self.B), dtype=torch.bfloat16,
+                                       device=self.device)
         check_dp_args(dp_clip, dp_noise)
         self.dp_clip, self.dp_noise = float(dp_clip), float(dp_noise)
         self.dp = self.dp_clip > 0.0
@@ -260,7 +323,30 @@ class FusedTinyTrainer:
             slab_stride=self.stride, B=self.B, lr=self.lr, momentum=self.momentum, wd=self.wd,
             nesterov=int(self.nesterov), prec=self.prec, dp_clip=self.dp_clip, dp_sigma=self.dp_noise,
             dp_seed=self.dp_seed, dp_scale=_lib.ptr(self.dp_scale), dp_step=_lib.ptr(self.dp_step),
-            xbg=_lib.ptr(self.xbg))
+            xbg=_lib.ptr(self.xbg), xpk=_lib.ptr(self.xpk), prepack=_lib.PREPACK[self.prepack])
+
+    def _alloc_prepacked(self) -> None:
+        """Allocate and fill the packed shard, or record why not and keep the unpacked path."""
+        N, L = self.x.shape
+        need = 2 * _lib.kernels().ecg_tiny_pack_halfs(L, N)
+        free, _total = torch.cuda.mem_get_info(self.device)
+        if need > self.prepack_share * free:
+            self.prepack_fallback = (f"packed shard of {need} B exceeds {self.prepack_share:g} of the {free} B free")
+        else:
+            try:
+                self.xpk = torch.empty((N, need // (2 * N)), dtype=torch.bfloat16, device=self.device)
+            except torch.cuda.OutOfMemoryError as e:
+                self.prepack_fallback = f"allocation of {need} B failed: {e}"
+        if self.xpk is None:
+            self.prepack = "none"
+        else:
+            self.repack()
+
+    def repack(self) -> None:
+        """Rebuild the packed shard from ``self.x`` (enqueued on the current stream): call it after rewriting the
+        windows in place.  Without a packed shard there is nothing to do."""
+        if self.xpk is not None:
+            pack_dataset(self.x, self.xpk)
 
     # ------------------------------------------------------------------ graph management
     def _round_of(self, n: int, table: torch.Tensor):

@@ -15,6 +15,10 @@
 // (xg) and as packed bf16 rows with the conv padding written out as zeros (xbg, kPackLead); a round's steps s > 0 run
 // the PK variant of the step kernel, whose conv1 operand is one 16-byte load of such a row and a one-element shift -
 // conversion, edge shifts and bounds handling are done once per element by the gather, not 7 times per step here.
+// The dataset itself does not change while a trainer lives, so it can be packed once (tiny_pack_rows_kernel, xpk): the
+// gather blocks then only copy packed rows (kPrepackGather), or there is no gather at all and the PK kernel loads
+// idx[b] and reads its row from the packed dataset (MODE 4, kPrepackDirect - the default of FusedTinyTrainer: 9.45-9.52
+// against 9.76-9.81 us/step with the per-step gather, 9.58-9.64 with the copying gather; profiles/r15/tiny_prepacked.txt).
 // (One launch per step with an in-kernel last-arriver reduction tree and one persistent launch per round were
 // measured slower - 13.23 and 16.33 vs 10.62 us/step, profiles/r4/tiny_phase_diag.txt - and were removed in round 5.)
 //
@@ -76,6 +80,10 @@ __device__ __forceinline__ void st_wt(__amdgpu_buffer_rsrc_t r, int idx, float v
 __device__ __forceinline__ void st_wt4(__amdgpu_buffer_rsrc_t r, int idx, f32x4 v) {  // idx: float index, 16-B aligned
   typedef int i32x4 __attribute__((ext_vector_type(4)));
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), r, idx * 4, 0, 16);
+}
+__device__ __forceinline__ void st_wt_b128(__amdgpu_buffer_rsrc_t r, int byte_off, u32x4 v) {  // 16-byte aligned
+  typedef int i32x4 __attribute__((ext_vector_type(4)));
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), r, byte_off, 0, 16);
 }
 __device__ __forceinline__ void st_wt_b64(__amdgpu_buffer_rsrc_t r, int byte_off, u32x2 v) {  // 8-byte aligned
   __builtin_amdgcn_raw_buffer_store_b64(v, r, byte_off, 0, 16);
@@ -969,6 +977,12 @@ struct TinySample {
 // (the PK kernel never reads it).  A pointer or long that straddles dword 14 would not be preloaded at all: keep the
 // 8-byte arguments on even dwords when this list changes.  The code is also correct where the firmware does not
 // preload: the compiler's prologue then loads the same dwords.
+// MODE 4: MODE 0 of the PK kernel on the dataset packed once (tiny_pack_rows_kernel) instead of gathered rows: workgroup
+//         b reads packed row idx[b] of X and label Y[idx[b]] itself.  The pitch of packed rows follows from L
+//         (pack_ldb), so the ``ldx`` argument is free and carries the address of this step's ``idx`` row: it lies
+//         inside the preloaded dwords, and the chain in front of the window loads is one scalar round trip (idx[b]),
+//         not two (the idx pointer from the kernarg segment, then idx[b]).  A new instantiation: MODE 0's code is
+//         untouched.
 // MODE 3: MODE 0 for a cohort of M virtual clients of B windows each in one launch, grid (B, M).  Workgroup (x, c)
 //         works on row c * B + x of the M * B rows (``idx``, the gathered rows and the slab hold the clients' rows back
 //         to back) with client c's weights and image, which lie at the fixed strides cohort_pstride /
@@ -979,7 +993,7 @@ constexpr int kCohortWprepStride = (WP_BYTES + 127) / 128 * 128;                
 
 template <int WAVES, int MODE, bool F32, bool PF, bool PK = false>
 __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
-    const float* __restrict__ X, long ldx,               // dataset windows [N, ldx]
+    const float* __restrict__ X, long ldx,               // dataset windows [N, ldx]; MODE 4: ldx carries ``idx``
     const unsigned char* __restrict__ wprep,             // PF image of ``params`` (PF only)
     const int* __restrict__ Y,                           // [N] int32 labels (unused in MODE 1)
     unsigned long long* __restrict__ stamps,             // diagnostic phase clock (nullptr = off)
@@ -993,6 +1007,8 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
   TinySample<WAVES, F32, PF, PK> S(smem, L, nc);
   constexpr bool TRAIN = MODE != 1;
   constexpr bool COHORT = MODE == 3;
+  constexpr bool PKI = MODE == 4;
+  static_assert(!PKI || PK, "MODE 4 reads packed rows");
   const int tid = threadIdx.x;
   const int b = COHORT ? blockIdx.y * gridDim.x + blockIdx.x : blockIdx.x;
   const long rows = COHORT ? (long)gridDim.x * gridDim.y : (long)gridDim.x;
@@ -1018,10 +1034,18 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     // "inputs issued, pads written", not a barrier; the wait for the window is counted in phase 1.
     int ylab = 0;
     long row = b;  // PK: gathered rows, read in place (launch_step rejects an idx), so ``idx`` is never waited for
-    if constexpr (!PK) row = idx ? (long)idx[b] : (long)b;
-    const float* xrow = X + row * ldx;
+    long pitch = ldx;
+    if constexpr (PKI) {
+      // one scalar load, its address made of preloaded dwords only; the constant address space keeps it scalar
+      typedef const __attribute__((address_space(4))) int* IdxPtr;
+      row = ((IdxPtr)ldx)[b];
+      pitch = pack_ldb(L) / 2;
+    } else if constexpr (!PK) {
+      row = idx ? (long)idx[b] : (long)b;
+    }
+    const float* xrow = X + row * pitch;
     // exactly the row (bf16); PK: the whole packed row, pads included
-    [[maybe_unused]] const __amdgpu_buffer_rsrc_t xr = make_rsrc(xrow, PK ? ldx * 4 : (long)L * 4);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t xr = make_rsrc(xrow, PK ? pitch * 4 : (long)L * 4);
     [[maybe_unused]] typename TinySample<WAVES, F32, PF, PK>::X1 x0;
     [[maybe_unused]] float hv_pk = 0.f;
     if constexpr (PK) {
@@ -1089,7 +1113,7 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     ECG_STAMP(3)
     S.template head_and_M<TRAIN>(ylab, inv_B, out, out_stride, b);
     if (!TRAIN) return;
-    if (MODE == 0 && stamps && (tid & 63) == 0 && (S.w <= 1 || S.w == WAVES - 1))  // diagnostic: head / M wave ends
+    if ((MODE == 0 || PKI) && stamps && (tid & 63) == 0 && (S.w <= 1 || S.w == WAVES - 1))  // diagnostic: head / M wave ends
       stamps[(long)b * 16 + 8 + (S.w == 0 ? 0 : S.w == 1 ? 1 : 2)] = __builtin_amdgcn_s_memtime();
     __syncthreads();
     ECG_STAMP(4)
@@ -1146,9 +1170,15 @@ struct GatherArgs {
   int L, ldg, B, vec;  // vec: 16-byte rows (L % 4 == 0, ldx % 4 == 0, X 16-byte aligned)
   __bf16* xbg;         // [B][ldb] packed bf16 rows (kPackLead comment), written write-through; nullptr: none
   int ldb;
+  const __bf16* xpk;   // [N][ldb] the whole dataset as packed rows (tiny_pack_rows_kernel); nullptr: none.  With it
+                       // the blocks copy packed rows xpk[idx[b]] -> xbg[b] and the labels: X and xg are not touched
 };
-__host__ __device__ inline int gather_rows_per_block(int L, int vec, int nt) {
-  const int per_row = vec ? L / 4 : L;
+// Threads that share one row - one per element, per 4 floats (vec) or, for packed source rows, per 16 bytes - and
+// the rows a block of ``nt`` threads takes.
+__host__ __device__ inline int gather_per_row(const GatherArgs& ga) {
+  return ga.xpk ? ga.ldb / 8 : ga.vec ? ga.L / 4 : ga.L;
+}
+__host__ __device__ inline int gather_rows_per_block(int per_row, int nt) {
   return per_row >= nt ? 1 : nt / per_row;
 }
 
@@ -1156,13 +1186,26 @@ __host__ __device__ inline int gather_rows_per_block(int L, int vec, int nt) {
 // element (vec: 4 elements) per thread and pass.  With ``xbg`` each thread also stores the bf16 of what it loaded -
 // the same cast as the step kernel's ecg::to_bf16 - and the row's threads share out its zero pads: the whole packed
 // row is written every time, and X is read once.
+// With ``xpk`` (the dataset packed once, tiny_pack_rows_kernel) a row is ldb / 8 threads that each move 16 bytes of
+// the packed row xpk[idx[b]], pads included, to xbg[b]: no fp32 is read, nothing is converted and xg is not written.
 template <int NT>
 __device__ __forceinline__ void gather_block(const GatherArgs& ga, int nred) {
-  const int per_row = ga.vec ? ga.L / 4 : ga.L;
-  const int rpb = gather_rows_per_block(ga.L, ga.vec, NT);
+  const int per_row = gather_per_row(ga);
+  const int rpb = gather_rows_per_block(per_row, NT);
   const int r0 = ((int)blockIdx.x - nred) * rpb;
-  const __amdgpu_buffer_rsrc_t xr = make_rsrc(ga.xg, (long)ga.B * ga.ldg * 4);
   const __amdgpu_buffer_rsrc_t br = make_rsrc(ga.xbg, ga.xbg ? (long)ga.B * ga.ldb * 2 : 0);
+  if (ga.xpk) {  // (launch-uniform)
+    for (int e = threadIdx.x; e < rpb * per_row; e += NT) {
+      const int lr_ = e / per_row, j = e - lr_ * per_row, b = r0 + lr_;
+      if (b >= ga.B) break;
+      const long row = ga.idx[b];
+      const u32x4 v = *reinterpret_cast<const u32x4*>(ga.xpk + row * ga.ldb + 8 * j);
+      st_wt_b128(br, (b * ga.ldb + 8 * j) * 2, v);
+      if (j == 0) ga.yg[b] = ga.Y[row];
+    }
+    return;
+  }
+  const __amdgpu_buffer_rsrc_t xr = make_rsrc(ga.xg, (long)ga.B * ga.ldg * 4);
   const int npad = ga.ldb - ga.L;  // pad elements of a packed row: kPackLead in front, the rest behind the data
   for (int e = threadIdx.x; e < rpb * per_row; e += NT) {
     const int lr_ = e / per_row, j = e - lr_ * per_row, b = r0 + lr_;
@@ -1500,6 +1543,44 @@ __global__ __launch_bounds__(NT) void cohort_dp_mean_kernel(
   global_params[i] = g + server_lr * (s * inv_M + noise);
 }
 
+// The whole dataset as packed rows, once: out[n] = [kPackLead zeros][bf16(X[n][0 .. L-1])][zeros up to ldb] for every
+// row n < N - the layout and the cast (ecg::to_bf16) of gather_block's xbg rows, so a step that reads out[idx[b]]
+// sees the bits it would have seen in the gathered row.  One block per row (rows beyond the grid: grid stride); every
+// element of a row, pads included, is written on every call.  VEC (4 | L, 4 | ldx, X 16-byte aligned): a thread takes
+// 4 packed elements - which lie wholly in the data or wholly in a pad, 4 dividing L, kPackLead and ldb - with one
+// 16-byte load and one 8-byte store; otherwise one element per thread and pass.
+template <bool VEC>
+__global__ __launch_bounds__(128) void tiny_pack_rows_kernel(const float* __restrict__ X, long ldx, long N, int L,
+                                                             __bf16* __restrict__ out) {
+  const int ldb = pack_ldb(L);
+  for (long n = blockIdx.x; n < N; n += gridDim.x) {
+    const float* x = X + n * ldx;
+    __bf16* o = out + n * ldb;
+    if constexpr (VEC) {
+      for (int u = threadIdx.x; u < ldb / 4; u += blockDim.x) {
+        const int j = 4 * u - kPackLead;  // first source element of the unit
+        bf16x4 p;
+        if (j >= 0 && j < L) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(x + j);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) p[q] = ecg::to_bf16(v[q]);
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) p[q] = ecg::to_bf16(0.f);
+        }
+        *reinterpret_cast<bf16x4*>(o + 4 * u) = p;
+      }
+    } else {
+      for (int e = threadIdx.x; e < ldb; e += blockDim.x) {
+        const int j = e - kPackLead;
+        const bool in = j >= 0 && j < L;  // the pad is chosen as bits: this file is built without signed zeros
+        const unsigned short v = __builtin_bit_cast(unsigned short, ecg::to_bf16(x[in ? j : 0]));
+        reinterpret_cast<unsigned short*>(o)[e] = in ? v : (unsigned short)0;
+      }
+    }
+  }
+}
+
 unsigned long long* g_stamps = nullptr;  // diagnostic phase stamps (ecg_tiny_set_stamps)
 
 FusedOpt no_fuse() {
@@ -1524,7 +1605,8 @@ struct StepArgs {
   int out_stride, B;
   float inv_B;
   const unsigned char* wprep;  // PF image of ``params`` (bf16 only); nullptr: operands built in LDS from ``params``
-  bool packed = false;  // X holds packed bf16 rows (PK kernel: MODE 0, bf16, wprep; idx == nullptr)
+  bool packed = false;  // X holds packed bf16 rows (PK kernel: MODE 0, bf16, wprep): gathered rows (idx == nullptr) or,
+                        // with an idx, the dataset packed once at pitch pack_ldb(L) (MODE 4; ldx is not read)
 };
 
 // MODE 3 (cohort): grid (a.B, M), ``a.params`` / ``a.wprep`` client 0's, ``a.out`` the M * a.B-row slab.
@@ -1534,8 +1616,9 @@ int launch_step(const StepArgs& a, hipStream_t stream, int M = 1) {
   auto kern = tiny_ecg_step_kernel<WAVES, MODE, F32, PF, PK>;
   if (sm.bytes > 64 * 1024)
     ECG_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, sm.bytes));
-  if (PK && a.idx) return ecg::kBadArg;  // the PK kernel reads row b
-  hipLaunchKernelGGL(kern, dim3(a.B, M), dim3(WAVES * 64), sm.bytes, stream, a.X, a.ldx, PF ? a.wprep : nullptr, a.Y,
+  if (PK && (MODE == 4) != (a.idx != nullptr)) return ecg::kBadArg;  // MODE 0 reads row b, MODE 4 row idx[b]
+  const long ldx = MODE == 4 ? (long)reinterpret_cast<uintptr_t>(a.idx) : a.ldx;  // (MODE 4 comment at the kernel)
+  hipLaunchKernelGGL(kern, dim3(a.B, M), dim3(WAVES * 64), sm.bytes, stream, a.X, ldx, PF ? a.wprep : nullptr, a.Y,
                      g_stamps, a.L, a.nc, a.params, a.out, a.out_stride, a.inv_B, a.idx, no_fuse().slab_wt);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
@@ -1595,9 +1678,12 @@ int step_dispatch(int mode, int prec, const StepArgs& a, hipStream_t stream) {
   if (a.wprep && prec == 1) return ecg::kBadArg;
   const int waves = pick_waves(a.L, prec == 1);
   if (a.packed) {
-    if (mode != 0 || prec != 0 || !a.wprep || a.idx) return ecg::kBadArg;
-    return waves == 8 ? launch_step<8, 0, false, true, true>(a, stream)
-                      : launch_step<16, 0, false, true, true>(a, stream);
+    if (mode != 0 || prec != 0 || !a.wprep) return ecg::kBadArg;
+    if (!a.idx)
+      return waves == 8 ? launch_step<8, 0, false, true, true>(a, stream)
+                        : launch_step<16, 0, false, true, true>(a, stream);
+    return waves == 8 ? launch_step<8, 4, false, true, true>(a, stream)
+                      : launch_step<16, 4, false, true, true>(a, stream);
   }
   if (prec == 1) return dispatch_cfg<true, false>(mode, waves, a, stream);
   if (a.wprep) return dispatch_cfg<false, true>(mode, waves, a, stream);
@@ -1626,7 +1712,7 @@ RedGeom red_geom(int P, int M, const GatherArgs* gather, bool cohort = false) {
   g.nred = (gather || cohort) ? g.grid : INT_MAX;
   if (gather) {
     g.ga = *gather;
-    const int rpb = gather_rows_per_block(g.ga.L, g.ga.vec, kRedThreads);
+    const int rpb = gather_rows_per_block(gather_per_row(g.ga), kRedThreads);
     g.grid += (g.ga.B + rpb - 1) / rpb;
   }
   return g;
@@ -1806,7 +1892,16 @@ struct EcgTinyRound {
   unsigned long long* dp_step;
   void* xbg;  // bf16 [2][B][ldb] (ecg_tiny_gather_halfs; nullable, needs xg): the gather also writes each window as
               // a packed bf16 row into buffer (s + 1) & 1, and step s + 1 runs the kernel that reads those (PK)
+  // The dataset packed once (ecg_tiny_pack_dataset; bf16 [N][pack_ldb(L)], nullable) and what a round does with it:
+  //   kPrepackGather  the gather blocks copy packed rows xpk[idx[b]] -> xbg[b] (16 bytes per thread) and the labels;
+  //                   X is read by the round's first step only.  Needs wprep, idx, yg and xbg; takes no xg.
+  //   kPrepackDirect  no gather: steps s > 0 run the PK kernel on xpk itself (MODE 4: row idx[b], label Y[idx[b]]).
+  //                   Needs wprep and idx; takes no xg, yg or xbg.
+  // Without xpk, ``prepack`` is kPrepackNone.  Every form computes the same bits.
+  const void* xpk;
+  int prepack;
 };
+enum { kPrepackNone = 0, kPrepackGather = 1, kPrepackDirect = 2 };
 
 ECG_API int ecg_tiny_round_sizeof(void) { return (int)sizeof(EcgTinyRound); }
 
@@ -1814,8 +1909,17 @@ static int check_round(const EcgTinyRound* r) {
   if (!r || r->steps < 1 || !r->X || !r->Y || !r->params || !r->slab) return ecg::kBadArg;
   if (r->prec != 0 && r->prec != 1) return ecg::kBadArg;
   if (r->wprep && r->prec != 0) return ecg::kBadArg;
-  if ((!r->xg) != (!r->yg) || (r->xg && (!r->wprep || !r->idx))) return ecg::kBadArg;
-  if (r->xbg && !r->xg) return ecg::kBadArg;
+  if (r->prepack == kPrepackNone) {
+    if (r->xpk) return ecg::kBadArg;
+    if ((!r->xg) != (!r->yg) || (r->xg && (!r->wprep || !r->idx))) return ecg::kBadArg;
+    if (r->xbg && !r->xg) return ecg::kBadArg;
+  } else {
+    if (r->prepack != kPrepackGather && r->prepack != kPrepackDirect) return ecg::kBadArg;
+    if (!r->xpk || !r->wprep || !r->idx || r->xg) return ecg::kBadArg;
+    const bool bufs = r->prepack == kPrepackGather;  // the packed ping-pong and its labels: both or neither
+    if ((r->yg != nullptr) != bufs || (r->xbg != nullptr) != bufs) return ecg::kBadArg;
+    if (reinterpret_cast<uintptr_t>(r->xpk) % 16 != 0) return ecg::kBadArg;
+  }
   if (r->dp_clip < 0.f || r->dp_sigma < 0.f || (r->dp_sigma > 0.f && r->dp_clip == 0.f)) return ecg::kBadArg;
   if (r->dp_clip > 0.f && (!r->dp_scale || !r->dp_step)) return ecg::kBadArg;
   return check_step_args(r->L, r->nc, r->B, r->slab_stride, 0, r->prec == 1);
@@ -1825,29 +1929,31 @@ static int check_round(const EcgTinyRound* r) {
 // (nullable) the packed bf16 rows xbg [2][rows][ldb].  Step s > 0 reads buffer s & 1, which the reduce launch of step
 // s - 1 filled (stream order: that buffer's previous reader, step s - 2's kernel, finished before that reduce
 // started).  With xbg the step reads the packed rows instead of xg (xg is still written: it is the unpacked kernel's
-// input and the record of what was gathered).
+// input).  With ``xpk``, the dataset packed once, there is no xg at all: the gather copies packed rows into xbg.
 struct GatherBufs {
   float* xg;
   int* yg;
   __bf16* xbg;
+  const __bf16* xpk = nullptr;
 };
 // What every gather launch of the round shares; gather_fill sets the rest.
 static GatherArgs gather_args(const float* X, long ldx, const int* Y, int L, int rows) {
   const int vec = (L % 4 == 0 && ldx % 4 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0) ? 1 : 0;
-  return {X, ldx, nullptr, Y, nullptr, nullptr, L, (L + 3) / 4 * 4, rows, vec, nullptr, pack_ldb(L)};
+  return {X, ldx, nullptr, Y, nullptr, nullptr, L, (L + 3) / 4 * 4, rows, vec, nullptr, pack_ldb(L), nullptr};
 }
 // The reduce launch of step s gathers step s + 1's batch ``idx_next`` into buffer (s + 1) & 1.
 static void gather_fill(GatherArgs& ga, const GatherBufs& g, int s, const int* idx_next) {
   const long buf = (long)((s + 1) & 1) * ga.B;
   ga.idx = idx_next;
-  ga.xg = g.xg + buf * ga.ldg;
+  ga.xg = g.xg ? g.xg + buf * ga.ldg : nullptr;
   ga.yg = g.yg + buf;
   ga.xbg = g.xbg ? g.xbg + buf * ga.ldb : nullptr;
+  ga.xpk = g.xpk;
 }
 // Step s reads buffer s & 1 by row.
 static void gather_read(StepArgs& a, const GatherArgs& ga, const GatherBufs& g, int s) {
   const long buf = (long)(s & 1) * ga.B;
-  a.X = g.xg + buf * ga.ldg;
+  a.X = g.xg ? g.xg + buf * ga.ldg : nullptr;  // (null with xpk: the packed rows below)
   a.ldx = ga.ldg;
   a.idx = nullptr;
   a.Y = g.yg + buf;
@@ -1864,15 +1970,21 @@ static void gather_read(StepArgs& a, const GatherArgs& ga, const GatherBufs& g, 
 static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
   const int P = make_layout(r.nc).P;
   unsigned char* wprep = static_cast<unsigned char*>(r.wprep);
-  const GatherBufs bufs{r.xg, r.yg, static_cast<__bf16*>(r.xbg)};
+  const __bf16* xpk = static_cast<const __bf16*>(r.xpk);
+  const bool gathers = r.xg || r.prepack == kPrepackGather;
+  const GatherBufs bufs{r.xg, r.yg, static_cast<__bf16*>(r.xbg), r.prepack == kPrepackGather ? xpk : nullptr};
   GatherArgs ga = gather_args(r.X, r.ldx, r.Y, r.L, r.B);
   for (int s = 0; s < r.steps; ++s) {
     const int* idx = r.idx ? r.idx + (long)s * r.B : nullptr;
-    const bool gather_next = r.xg && s + 1 < r.steps;
+    const bool gather_next = gathers && s + 1 < r.steps;
     if (gather_next) gather_fill(ga, bufs, s, idx + r.B);
     StepArgs a{r.X, r.L, r.ldx, idx, r.Y, r.params, r.nc, r.slab, r.slab_stride, r.B, 1.0f / (float)r.B,
                s == 0 ? nullptr : wprep};
-    if (r.xg && s > 0) gather_read(a, ga, bufs, s);
+    if (gathers && s > 0) gather_read(a, ga, bufs, s);
+    if (r.prepack == kPrepackDirect && s > 0) {  // the PK kernel on the packed dataset itself, row idx[b]
+      a.X = reinterpret_cast<const float*>(xpk);
+      a.packed = true;
+    }
     int st = step_dispatch(0, r.prec, a, stream);
     if (st) return st;
     if (r.dp_clip > 0.f)
@@ -1938,6 +2050,24 @@ ECG_API long ecg_tiny_gather_floats(int L, int B) { return 2L * B * ((L + 3) / 4
 
 // bf16 elements of the packed gather buffer ``xbg`` of a round.
 ECG_API long ecg_tiny_gather_halfs(int L, int B) { return 2L * B * pack_ldb(L); }
+
+// bf16 elements of the dataset packed once (``EcgTinyRound::xpk``): N rows of pack_ldb(L).
+ECG_API long ecg_tiny_pack_halfs(int L, long N) { return N * pack_ldb(L); }
+
+// Pack the dataset X [N][ldx] (window length L) into ``out`` [N][pack_ldb(L)], 16-byte aligned: every row, pads
+// included, is written (tiny_pack_rows_kernel).  Callers repeat it after they rewrite X.
+ECG_API int ecg_tiny_pack_dataset(const float* X, long ldx, long N, int L, void* out, hipStream_t stream) {
+  if (!X || !out || N <= 0 || L < 1 || ldx < L || reinterpret_cast<uintptr_t>(out) % 16 != 0) return ecg::kBadArg;
+  const bool vec = L % 4 == 0 && ldx % 4 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0;
+  const unsigned grid = (unsigned)(N < (1L << 20) ? N : (1L << 20));  // rows beyond it: the kernel's grid stride
+  __bf16* o = static_cast<__bf16*>(out);
+  if (vec)
+    hipLaunchKernelGGL(tiny_pack_rows_kernel<true>, dim3(grid), dim3(128), 0, stream, X, ldx, N, L, o);
+  else
+    hipLaunchKernelGGL(tiny_pack_rows_kernel<false>, dim3(grid), dim3(128), 0, stream, X, ldx, N, L, o);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
 
 ECG_API int ecg_round_graph_launch(void* handle, hipStream_t stream) {
   if (!handle) return ecg::kBadArg;
