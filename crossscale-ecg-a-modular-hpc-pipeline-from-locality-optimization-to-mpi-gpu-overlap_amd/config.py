@@ -73,6 +73,11 @@ class FedAvgConfig:
     server_beta1: float = 0.9
     server_beta2: float = 0.99
     server_tau: float = 1e-3
+    # where the server step of a cohort round is taken (rank | global; global needs clients_per_gpu > 1): "rank" inside
+    # every rank's round on that rank's delta, the driver then averaging the stepped weights; "global" after an
+    # all-reduce of the ranks' deltas, one replicated step on every rank (what adagrad, adam and yogi need under
+    # sync fedavg on more than one rank)
+    server_scope: str = "rank"
     results_csv: str = "results/fedavg_results.csv"
     jsonl: Optional[str] = None
     model: str = "tiny_ecg"

@@ -81,7 +81,7 @@ class TinyCohortRound(C.Structure):
                 ("fanout", i32), ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32),
                 ("cdp_clip", f32), ("cdp_sigma", f32), ("server_lr", f32), ("cdp_seed", u64), ("cdp_scale", vp),
                 ("cdp_norm", vp), ("cdp_round", vp), ("server_opt", i32), ("server_beta1", f32), ("server_beta2", f32),
-                ("server_tau", f32), ("server_m", vp), ("server_v", vp)]
+                ("server_tau", f32), ("server_m", vp), ("server_v", vp), ("server_delta", vp)]
 
 
 def _bind_kernels(lib: C.CDLL) -> None:
@@ -114,6 +114,8 @@ def _bind_kernels(lib: C.CDLL) -> None:
     _sig(lib, "ecg_cohort_dp_noise", [vp, i32, u64, u64, vp])
     _sig(lib, "ecg_cohort_server_close", [vp, vp, i32, i32, f32, f32, f32, u64, vp, vp, vp, i32, f32, f32, f32, vp, vp,
                                           vp])
+    _sig(lib, "ecg_cohort_delta_close", [vp, vp, i32, i32, f32, f32, u64, vp, vp, vp, vp, vp])
+    _sig(lib, "ecg_server_opt_step", [vp, vp, i64, i32, f32, f32, f32, f32, vp, vp, vp])
     _sig(lib, "ecg_tiny_cohort_param_stride", [i32])
     _sig(lib, "ecg_tiny_cohort_wprep_stride", [])
     _sig(lib, "ecg_tiny_gather_floats", [i32, i32], i64)

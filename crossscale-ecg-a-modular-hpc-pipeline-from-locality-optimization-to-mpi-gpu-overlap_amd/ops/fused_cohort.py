@@ -19,6 +19,13 @@ A server optimizer (``server_opt`` sgdm / adagrad / adam / yogi; ``train/server_
 ``cohort_server_opt_kernel`` in place of ``cohort_dp_mean_kernel``: the same averaged, clipped, noised delta, then the
 optimizer's update of its state ``server_m`` / ``server_v`` ([P] fp32 device tensors this trainer owns, kept across
 rounds, rolled back by ``prepare``, saved and restored with ``server_state`` / ``load_server_state``) and its step.
+
+``server_scope="global"`` splits that close where the delta exists, for drivers of several ranks that want ONE server
+optimizer over all their clients: the round graph ends with ``cohort_delta_scale_kernel`` + ``cohort_delta_kernel``,
+which leave this rank's averaged, clipped, noised delta in ``server_delta`` ([P] fp32) and the global weights, m and v
+untouched; the driver all-reduces ``server_delta`` and ``apply_server_step`` (``server_step_kernel``) then takes the
+step - the plain one for ``server_opt="none"`` - on every rank alike.  On one rank the two halves leave the bits of the
+default ``server_scope="rank"``.
 """
 from __future__ import annotations
 
@@ -34,7 +41,7 @@ from ..models.tiny_ecg import TinyECG, num_params
 from .fused_tiny import _check_dataset, labels_int32, prec_id, slab_stride
 from .tiny_eval import EvalResult, TinyEvaluator, tiny_evaluate
 from ..train.cohort import check_client_dp, client_dp_seed_of, client_dp_sigma_share, load_server_state
-from ..train.server_opt import BETA1, BETA2, TAU, check_server_opt, server_opt_init
+from ..train.server_opt import BETA1, BETA2, TAU, check_server_opt, check_server_scope, server_opt_init
 
 
 class FusedCohortTrainer:
@@ -47,12 +54,13 @@ class FusedCohortTrainer:
                  use_graph: Optional[bool] = None, precision: str = "bf16", dp_clip: float = 0.0,
                  client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
                  server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
-                 server_beta2: float = BETA2, server_tau: float = TAU):
+                 server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank"):
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients: the cohort "
                              "reduce has no per-sample clip")
         check_client_dp(client_dp_clip, client_dp_noise, server_lr, world_size)
         self.server_opt_id = check_server_opt(server_opt, server_beta1, server_beta2, server_tau)
+        self.server_scope = check_server_scope(server_scope)
         self.device = x_gpu.device
         self.precision = precision
         self.prec = prec_id(precision)
@@ -109,7 +117,11 @@ class FusedCohortTrainer:
         self.server_opt = server_opt
         self.server_beta1, self.server_beta2, self.server_tau = float(server_beta1), float(server_beta2), float(server_tau)
         self.server_m, self.server_v = server_opt_init(server_opt, self.P, self.server_tau, self.device)
-        self.client_dp = self.cdp_clip > 0.0 or self.server_lr != 1.0 or server_opt != "none"
+        # scope "global": the round ends with this rank's delta in server_delta (written in place: graphs hold its
+        # address) and always takes the two-launch close, so the factor, norm and round-word buffers always exist
+        split = self.server_scope == "global"
+        self.server_delta = torch.zeros(self.P, **f32) if split else None
+        self.client_dp = self.cdp_clip > 0.0 or self.server_lr != 1.0 or server_opt != "none" or split
         self.cdp_scale = self.cdp_norm = self.cdp_round = None
         if self.client_dp:
             self.cdp_scale = torch.ones(self.M, **f32)
@@ -126,7 +138,9 @@ class FusedCohortTrainer:
             r.cdp_clip, r.cdp_sigma = self.cdp_clip, client_dp_sigma_share(self.cdp_noise, world_size)
             r.server_lr, r.cdp_seed = self.server_lr, self.cdp_seed
             r.cdp_scale, r.cdp_norm, r.cdp_round = (t.data_ptr() for t in (self.cdp_scale, self.cdp_norm, self.cdp_round))
-        if self.server_opt_id:
+        if split:  # (the struct's server_opt stays 0: apply_server_step takes the step, outside the round)
+            self._round.server_delta = self.server_delta.data_ptr()
+        elif self.server_opt_id:
             r = self._round
             r.server_opt, r.server_beta1, r.server_beta2 = self.server_opt_id, self.server_beta1, self.server_beta2
             r.server_tau, r.server_m, r.server_v = self.server_tau, _lib.ptr(self.server_m), _lib.ptr(self.server_v)
@@ -165,7 +179,8 @@ class FusedCohortTrainer:
         """Capture, upload and warm every round graph whose step count is in ``sizes`` (on both index tables).  The
         warm-up replays are rolled back: global weights, loss words, tables and the round counter - the device word of
         the DP close and the server optimizer's m / v with it - stay as found (the per-client buffers are scratch that
-        every round's fan-out rewrites)."""
+        every round's fan-out rewrites; so is ``server_delta`` of scope "global", whose graphs write neither the
+        weights nor m / v: no step has to be replayed or undone)."""
         if not self.use_graph:
             return
         lib = _lib.kernels()
@@ -249,8 +264,23 @@ class FusedCohortTrainer:
     def run_round(self, n_steps: Optional[int] = None, reset_loss: bool = True, next_n: Optional[int] = None) -> None:
         self.prepare_round(n_steps, reset_loss)
         self.launch_round(n_steps, next_n)
+        if self.server_delta is not None:
+            self.apply_server_step()
+
+    def apply_server_step(self) -> None:
+        """Scope "global": one server step on the global weights from ``server_delta`` - this rank's delta as
+        ``launch_round`` left it, or the ranks' average once the driver all-reduced it - with the trainer's optimizer
+        and constants (``server_opt="none"``: the plain step with ``server_lr``), enqueued on the current stream."""
+        if self.server_delta is None:
+            raise RuntimeError('apply_server_step needs server_scope="global": scope "rank" steps inside the round')
+        _lib.check(_lib.kernels().ecg_server_opt_step(
+            self.params.data_ptr(), self.server_delta.data_ptr(), self.P, self.server_opt_id, self.server_lr,
+            self.server_beta1, self.server_beta2, self.server_tau, _lib.ptr(self.server_m), _lib.ptr(self.server_v),
+            _lib.stream_ptr(self.device)), "ecg_server_opt_step")
 
     def launch_round(self, n_steps: Optional[int] = None, next_n: Optional[int] = None) -> None:
+        """Enqueue the staged round.  Scope "global": it ends with this rank's delta in ``server_delta`` and the global
+        weights as they were; ``apply_server_step`` completes it."""
         n = self._check_n(n_steps)
         table = self.take_staged(n)
         stream = _lib.stream_ptr(self.device)

@@ -232,12 +232,21 @@ class FedAvgRound:
 
     ``end_round(rec)`` is called after the round's local steps are enqueued; ``begin_round(rec_prev, prep)``
     before the next round's steps: it runs ``prep`` (weight-independent work) and then waits.
+
+    ``on_averaged`` (``none`` and ``tail`` only): a callable run once per completed collective, right after the wait
+    that completes it - in ``end_round`` for ``none``; for ``tail`` in the next ``begin_round``, after ``prep``, or in
+    ``finalize`` - when ``flat`` holds the average and before anything else reads it.  A caller that all-reduces
+    something other than the weights (a cohort round's delta) takes its step on the average there.
     """
 
-    def __init__(self, flat: torch.Tensor, comm: FedAvgComm, mode: str = "none"):
+    def __init__(self, flat: torch.Tensor, comm: FedAvgComm, mode: str = "none",
+                 on_averaged: Optional[Callable[[], None]] = None):
         if mode not in ("none", "tail", "delayed"):
             raise ValueError(f"unknown overlap mode {mode!r}")
-        self.flat, self.comm, self.mode = flat, comm, mode
+        if on_averaged is not None and mode == "delayed":
+            raise ValueError("on_averaged is not supported with overlap mode 'delayed': that mode all-reduces a "
+                             "snapshot and corrects flat one round late")
+        self.flat, self.comm, self.mode, self.on_averaged = flat, comm, mode, on_averaged
         self._pending: List[Pending] = []
         self._rec: Optional[CommRecord] = None
         if mode == "delayed":
@@ -259,8 +268,13 @@ class FedAvgRound:
         p = self.comm.issue(self.flat, rec)
         if self.mode == "none":
             self.comm.wait([p], rec)
+            self._averaged()
         else:
             self._pending, self._rec = [p], rec
+
+    def _averaged(self) -> None:
+        if self.on_averaged is not None:
+            self.on_averaged()
 
     def begin_round(self, prep=None) -> None:
         """Weight-independent work for the next round, then (tail) the wait for the averaged weights."""
@@ -269,6 +283,7 @@ class FedAvgRound:
         if self.mode == "tail" and self._pending:
             self.comm.wait(self._pending, self._rec)
             self._pending, self._rec = [], None
+            self._averaged()
 
     def _finish_delayed(self) -> None:
         if not self._pending:
@@ -302,3 +317,4 @@ class FedAvgRound:
         elif self._pending:
             self.comm.wait(self._pending, self._rec)
             self._pending, self._rec = [], None
+            self._averaged()

@@ -20,6 +20,10 @@ C / (M * W)), and ``z = philox.normal(client_dp_seed, round, P, stream=1)``: the
 A server optimizer (``server_opt`` sgdm / adagrad / adam / yogi; ``train/server_opt.py`` states the rules) takes the
 bracket above - Delta, the averaged, clipped, noised delta - as its pseudo-gradient in place of the plain step
 ``g + eta * Delta``; its state ``server_m`` / ``server_v`` lives across rounds (``server_state`` / ``load_server_state``).
+
+``server_scope="global"`` takes the same two phases apart: ``launch_round`` ends with Delta in ``server_delta`` (a
+tensor written in place) and the model untouched, and ``apply_server_step`` takes the plain step or the optimizer's on
+whatever ``server_delta`` then holds - the mean of the ranks' Deltas once a driver all-reduced it.
 """
 from __future__ import annotations
 
@@ -33,7 +37,8 @@ import torch.nn.functional as F
 
 from ..data.dataset import CohortSampler
 from ..utils import philox
-from .server_opt import BETA1, BETA2, TAU, check_server_opt, server_opt_init, server_opt_step
+from .server_opt import (BETA1, BETA2, TAU, check_server_opt, check_server_scope, server_opt_init,
+                         server_opt_step)
 
 
 class TorchCohortTrainer:
@@ -43,11 +48,12 @@ class TorchCohortTrainer:
                  amp_dtype: Optional[torch.dtype] = None, seed: Optional[int] = None, dp_clip: float = 0.0,
                  client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
                  server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
-                 server_beta2: float = BETA2, server_tau: float = TAU):
+                 server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank"):
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients")
         check_client_dp(client_dp_clip, client_dp_noise, server_lr, world_size)
         check_server_opt(server_opt, server_beta1, server_beta2, server_tau)
+        self.server_scope = check_server_scope(server_scope)
         self.model, self.x, self.y = model, x, y
         self.device = x.device
         self.B, self.S, self.K = int(batch_size), int(steps_per_round), int(clients)
@@ -72,7 +78,11 @@ class TorchCohortTrainer:
         self.server_beta1, self.server_beta2, self.server_tau = float(server_beta1), float(server_beta2), float(server_tau)
         self.server_m, self.server_v = server_opt_init(server_opt, sum(p.numel() for p in model.parameters()),
                                                        self.server_tau, self.device)
-        self.client_dp = self.cdp_clip > 0.0 or self.server_lr != 1.0 or server_opt != "none"
+        numel = sum(p.numel() for p in model.parameters())
+        self.server_delta = (torch.zeros(numel, dtype=torch.float32, device=self.device)
+                             if self.server_scope == "global" else None)
+        self.client_dp = (self.cdp_clip > 0.0 or self.server_lr != 1.0 or server_opt != "none"
+                          or self.server_delta is not None)
         self._norms: List[float] = []
         self._scales: List[float] = []
 
@@ -141,8 +151,15 @@ class TorchCohortTrainer:
         if self.cdp_nu != 0.0:
             z = philox.normal(self.cdp_seed, r, g.numel(), stream=1).astype(np.float32)
             upd = upd + torch.tensor(self.cdp_nu, **f32) * torch.from_numpy(z).to(self.device)
+        if self.server_delta is not None:  # scope "global": the round ends here; apply_server_step takes the step
+            self.server_delta.copy_(upd)
+            return
+        self._server_step(g, upd)
+
+    def _server_step(self, g: torch.Tensor, upd: torch.Tensor) -> None:
+        """The plain server step or the server optimizer's on the delta ``upd``, written into the model."""
         if self.server_opt == "none":
-            new = g + torch.tensor(self.server_lr, **f32) * upd
+            new = g + torch.tensor(self.server_lr, dtype=torch.float32, device=self.device) * upd
         else:
             new, self.server_m, self.server_v = server_opt_step(
                 self.server_opt, g, upd, self.server_m, self.server_v, self.server_lr, self.server_beta1,
@@ -153,6 +170,14 @@ class TorchCohortTrainer:
                 pg.copy_(new[off:off + pg.numel()].view_as(pg))
                 off += pg.numel()
 
+    def apply_server_step(self) -> None:
+        """Scope "global": one server step on the model from ``server_delta`` - this rank's delta as ``launch_round``
+        left it, or the ranks' average once the driver all-reduced it."""
+        if self.server_delta is None:
+            raise RuntimeError('apply_server_step needs server_scope="global": scope "rank" steps inside the round')
+        g = torch.cat([p.detach().reshape(-1) for p in self.model.parameters()]).float()
+        self._server_step(g, self.server_delta.clone())
+
     def last_clip_stats(self) -> Tuple[List[float], float]:
         """(the last round's delta norms in cohort order, the share of its clients that were clipped)."""
         return list(self._norms), sum(s < 1.0 for s in self._scales) / max(1, len(self._scales))
@@ -160,6 +185,8 @@ class TorchCohortTrainer:
     def run_steps(self, n: int, reset_loss: bool = True) -> None:
         self.prepare_round(n, reset_loss)
         self.launch_round(n)
+        if self.server_delta is not None:
+            self.apply_server_step()
 
     run_round = run_steps
 

@@ -56,8 +56,17 @@ MI355X execution (vs the reference's host-staged per-tensor MPI calls and per-st
     and is part of the per-rank checkpoint, so ``--resume`` continues it.  sgdm is linear in the delta: under ``--sync
     fedavg`` every rank keeps its own m and the unchanged all-reduce(AVG) of ``g + eta * m_rank`` is the global FedAvgM
     step with ``m = AVG(m_rank)``.  adagrad, adam and yogi are nonlinear in the delta and are rejected under ``--sync
-    fedavg`` on more than one rank (they would have to follow an all-reduce of the deltas); they run on one rank and
-    under ``--sync none``.
+    fedavg`` on more than one rank unless ``--server-scope global`` is given (they have to follow an all-reduce of the
+    deltas); they run on one rank and under ``--sync none``.
+  * ``--server-scope {rank,global}`` (default rank; global needs ``--clients-per-gpu``): with ``global`` a cohort round
+    ends with the rank's averaged, clipped, noised delta in ``trainer.server_delta`` and the weights untouched; under
+    ``--sync fedavg`` on several ranks that 5.8 KB buffer is all-reduced(AVG) in place of the weights and
+    ``trainer.apply_server_step`` - the plain step or the server optimizer's - runs on every rank right after the wait
+    that completes the collective (``FedAvgRound(on_averaged=...)``; ``--overlap tail``: after the next round's batch
+    preparation, before its launch).  Every rank steps from the same g, m, v and averaged delta, so weights and
+    optimizer state stay replicated, all five rules are exact, and m / v are global.  The mean of W deltas that each
+    carry a sigma / sqrt(W) noise share has the noise the accountant assumes.  Without a collective (one rank,
+    ``--sync none``) the step follows the round at once and ends on the bits of ``rank``.
 """
 from __future__ import annotations
 
@@ -84,7 +93,7 @@ from ..utils.ckpt import (ckpt_path, save_checkpoint, load_checkpoint, latest_ch
 from ..utils.csvio import (RoundStats, append_results, ROUND_COLUMNS, EVAL_COLUMNS, PRIVACY_COLUMNS,
                            COHORT_COLUMNS, CLIENT_PRIVACY_COLUMNS)
 from ..utils.philox import mix64
-from .server_opt import ADAPTIVE as ADAPTIVE_SERVER_OPTS, check_server_opt
+from .server_opt import ADAPTIVE as ADAPTIVE_SERVER_OPTS, check_server_opt, check_server_scope
 from ..utils.privacy import epsilon as dp_epsilon
 from ..utils.log import RankLogger
 from .local import TorchLocalTrainer
@@ -244,19 +253,26 @@ def check_server_opt_config(cfg: FedAvgConfig, ctx: DistContext) -> None:
     """A server optimizer acts on a cohort round's averaged client delta: it needs client sampling (and with it
     everything ``check_cohort_config`` asks for).  Under ``--sync fedavg`` on W > 1 ranks only sgdm is exact: its rule
     is linear in Delta, so the all-reduce(AVG) of the ranks' ``g + eta * m_rank`` is the global FedAvgM step with
-    ``m = AVG(m_rank)``; the adaptive rules are nonlinear in Delta and would have to follow the all-reduce."""
+    ``m = AVG(m_rank)``; the adaptive rules are nonlinear in Delta and have to follow an all-reduce of the deltas, which
+    is what ``--server-scope global`` does (for every rule, the plain step included; it needs client sampling too)."""
     check_server_opt(cfg.server_opt, cfg.server_beta1, cfg.server_beta2, cfg.server_tau)
+    check_server_scope(cfg.server_scope)
+    if cfg.server_scope == "global" and cfg.clients_per_gpu <= 1:
+        raise ValueError("--server-scope global needs client sampling (--clients-per-gpu K > 1): it all-reduces the "
+                         "mean of a cohort's client deltas and steps on the result")
     if cfg.server_opt == "none":
         return
     if cfg.clients_per_gpu <= 1:
         raise ValueError("--server-opt / --server-beta1 / --server-beta2 / --server-tau need client sampling "
                          "(--clients-per-gpu K > 1): the server optimizer steps on the mean of a cohort's client deltas")
-    if cfg.server_opt in ADAPTIVE_SERVER_OPTS and cfg.sync == "fedavg" and ctx.distributed and ctx.world_size > 1:
+    if (cfg.server_scope == "rank" and cfg.server_opt in ADAPTIVE_SERVER_OPTS and cfg.sync == "fedavg"
+            and ctx.distributed and ctx.world_size > 1):
         raise ValueError(f"--server-opt {cfg.server_opt} does not support --sync fedavg on more than one rank: its step "
                          "m / (sqrt(v) + tau) is nonlinear in the averaged delta, so it must follow the all-reduce of "
-                         "the ranks' deltas, and the driver all-reduces the weights after each rank's own step (the "
-                         "next item: all-reduce the deltas, then step); use --server-opt sgdm, whose rule is linear, "
-                         "one rank, or --sync none")
+                         "the ranks' deltas, and under --server-scope rank the driver all-reduces the weights after each "
+                         "rank's own step; use --server-scope global, which all-reduces the deltas and takes one "
+                         "replicated step on every rank, or --server-opt sgdm, whose rule is linear, one rank, or "
+                         "--sync none")
 
 
 def client_dp_world(cfg: FedAvgConfig, ctx: DistContext) -> int:
@@ -276,7 +292,8 @@ def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistCont
         kw = dict(clients=cfg.clients_per_gpu, cohort=cohort_size(cfg), lr=cfg.lr, momentum=cfg.momentum, seed=seed,
                   client_dp_clip=cfg.client_dp_clip, client_dp_noise=cfg.client_dp_noise, client_dp_seed=mix64(seed),
                   server_lr=cfg.server_lr, world_size=client_dp_world(cfg, ctx), server_opt=cfg.server_opt,
-                  server_beta1=cfg.server_beta1, server_beta2=cfg.server_beta2, server_tau=cfg.server_tau)
+                  server_beta1=cfg.server_beta1, server_beta2=cfg.server_beta2, server_tau=cfg.server_tau,
+                  server_scope=cfg.server_scope)
         if backend == "fused":
             from ..ops.fused_cohort import FusedCohortTrainer
             prec = "bf16" if (config_name == "G1" and cfg.amp_dtype == "bf16") else "fp32"
@@ -420,7 +437,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         log.info(f"[fedavg] {cname}: kernel backend {backend}")
         if cfg.server_opt != "none":
             log.event("server_opt", config=cname, server_opt=cfg.server_opt, server_lr=cfg.server_lr,
-                      beta1=cfg.server_beta1, beta2=cfg.server_beta2, tau=cfg.server_tau)
+                      beta1=cfg.server_beta1, beta2=cfg.server_beta2, tau=cfg.server_tau, scope=cfg.server_scope)
         start_round = _resume(cfg, cname, ctx, comm, model, trainer, log) if cfg.resume else 0
         if hasattr(trainer, "set_cohort_round"):  # the cohort sampler is a function of (seed, round): no other state
             trainer.set_cohort_round(start_round)
@@ -429,7 +446,14 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         mode = cfg.overlap if (fedavg and not weighted) else "none"
         # ResNet engine: the tail step applies SGD per backward segment and all-reduces each segment at once
         seg_tail = mode == "tail" and hasattr(trainer, "tail_fedavg")
-        fround = FedAvgRound(model_flat(model), fcomm, "none" if seg_tail else mode)
+        # --server-scope global: a cohort round ends with the rank's delta; under FedAvg the delta is what is
+        # all-reduced - not the weights: every rank takes the same step from the same g, m, v and averaged delta - and
+        # the step follows the wait that completes the collective; without a collective it follows the round at once
+        split = cfg.server_scope == "global" and cfg.clients_per_gpu > 1
+        if split and fedavg:
+            fround = FedAvgRound(trainer.server_delta, fcomm, mode, on_averaged=trainer.apply_server_step)
+        else:
+            fround = FedAvgRound(model_flat(model), fcomm, "none" if seg_tail else mode)
         if hasattr(trainer, "prepare"):  # capture + upload + warm the round graphs outside round 0's timing
             trainer.prepare([cfg.local_steps - 1 if seg_tail else cfg.local_steps])
         recs = []
@@ -466,6 +490,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                     _ddp_fused_round(trainer, ctx, n)
                 else:
                     trainer.launch_round(n)
+                    if split and not fedavg:
+                        trainer.apply_server_step()
                 if seg_tail:  # the round's last step, its segment all-reduces overlapping its own backward
                     trainer.tail_fedavg(fcomm, rec)
             m_l1 = fcomm.mark()

@@ -10,8 +10,10 @@ paper's ``v_{-1} >= tau^2``), no bias correction, everything in fp32:
 * ``yogi``:            ``m`` as adagrad,                    ``v = v - (1 - b2) Delta^2 sign(v - Delta^2)``, sign(0) = 0
 * adagrad, adam, yogi: ``g += eta m / (sqrt(v) + tau)`` with the new ``m`` and ``v``
 
-``eta`` is the server step size ``server_lr``.  This is the definition that ``cohort_server_opt_kernel`` of
-csrc/kernels/tiny_ecg_step.hip implements; ``server_opt_step`` is its torch form (the eager reference and the CPU path).
+``eta`` is the server step size ``server_lr``.  This is the definition that ``cohort_server_opt_kernel`` and, from
+Delta on, ``server_step_kernel`` of csrc/kernels/tiny_ecg_step.hip implement; ``server_opt_step`` is its torch form
+(the eager reference and the CPU path).  ``SERVER_SCOPES`` names where the step is taken: per rank on the rank's own
+Delta, or once ("global") on the all-reduced mean of the ranks' Deltas.
 """
 from __future__ import annotations
 
@@ -23,6 +25,16 @@ SERVER_OPTS = ("none", "sgdm", "adagrad", "adam", "yogi")
 SERVER_OPT_IDS = {name: i for i, name in enumerate(SERVER_OPTS)}  # EcgTinyCohortRound's server_opt
 ADAPTIVE = ("adagrad", "adam", "yogi")
 BETA1, BETA2, TAU = 0.9, 0.99, 1e-3
+# Where the server step is taken.  "rank": inside every rank's round, on that rank's delta (a driver of several ranks
+# then averages the stepped weights: exact for the linear rules only).  "global": the round stops at the delta, the
+# driver averages the ranks' deltas, and every rank takes the same step on the average (``apply_server_step``).
+SERVER_SCOPES = ("rank", "global")
+
+
+def check_server_scope(scope: str) -> str:
+    if scope not in SERVER_SCOPES:
+        raise ValueError(f"unknown server scope {scope!r}: one of {', '.join(SERVER_SCOPES)}")
+    return scope
 
 
 def check_server_opt(opt: str, beta1: float = BETA1, beta2: float = BETA2, tau: float = TAU) -> int:
@@ -49,18 +61,19 @@ def server_opt_init(opt: str, numel: int, tau: float, device) -> Tuple[Optional[
 
 
 def server_opt_step(opt: str, g: torch.Tensor, delta: torch.Tensor, m: torch.Tensor, v: Optional[torch.Tensor],
-                    eta: float, b1: float, b2: float, tau: float):
-    """One server step in fp32: ``(g_new, m_new, v_new)`` (``v_new`` is ``v`` for sgdm); the inputs are not written."""
+                    eta: float, b1: float, b2: float, tau: float, dtype: torch.dtype = torch.float32):
+    """One server step in fp32: ``(g_new, m_new, v_new)`` (``v_new`` is ``v`` for sgdm); the inputs are not written.
+    ``dtype=torch.float64`` evaluates the same rules in float64 on the fp32 constants (a reference for tests)."""
     if opt not in SERVER_OPT_IDS or opt == "none":
         raise ValueError(f"server_opt_step: no rule for {opt!r}")
-    c = lambda s: torch.tensor(s, dtype=torch.float32, device=g.device)  # noqa: E731  (a scalar, rounded once)
-    g, delta, m = g.float(), delta.float(), m.float()
+    c = lambda s: torch.tensor(s, dtype=torch.float32, device=g.device).to(dtype)  # noqa: E731  (rounded once, to fp32)
+    g, delta, m = g.to(dtype), delta.to(dtype), m.to(dtype)
     eta, b1, b2, tau, one = c(eta), c(b1), c(b2), c(tau), c(1.0)
     if opt == "sgdm":
         m = b1 * m + delta
         return g + eta * m, m, v
     m = b1 * m + (one - b1) * delta
-    v, d2 = v.float(), delta * delta
+    v, d2 = v.to(dtype), delta * delta
     if opt == "adagrad":
         v = v + d2
     elif opt == "adam":

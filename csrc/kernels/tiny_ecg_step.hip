@@ -2113,7 +2113,9 @@ ECG_API int ecg_tiny_cohort_wprep_stride(void) { return kCohortWprepStride; }
 // Client-level DP (cdp_clip > 0) and a server step size other than 1 replace the mean by the DP close
 // (cohort_delta_scale_kernel + cohort_dp_mean_kernel); with the cdp_* fields and server_lr all zero the round issues the
 // launches it always issued, cohort_mean_kernel included.  A server optimizer (server_opt != 0) closes the round with
-// cohort_delta_scale_kernel + cohort_server_opt_kernel; with server_opt == 0 the close is the one it was.
+// cohort_delta_scale_kernel + cohort_server_opt_kernel; with server_opt == 0 the close is the one it was.  With
+// ``server_delta`` the round stops where the delta exists (cohort_delta_scale_kernel + cohort_delta_kernel) and leaves
+// the server step to the caller (ecg_server_opt_step, after an all-reduce of the ranks' deltas).
 // ops/_lib.py mirrors this struct (TinyCohortRound) and checks its size against ecg_tiny_cohort_round_sizeof().
 struct EcgTinyCohortRound {
   const float* X;
@@ -2150,6 +2152,11 @@ struct EcgTinyCohortRound {
   float server_beta1, server_beta2, server_tau;
   float* server_m;
   float* server_v;
+  // The split close (nullable): [P], receives this round's averaged, clipped, noised delta - the value the closes above
+  // form, bit for bit - in place of any server step.  ``global_params`` then still holds the round's starting weights
+  // when the round ends, and server_opt, server_m and server_v are not read; it needs cdp_scale, cdp_norm and
+  // cdp_round.  Null: the round issues the launches it issues without this field.
+  float* server_delta;
 };
 
 ECG_API int ecg_tiny_cohort_round_sizeof(void) { return (int)sizeof(EcgTinyCohortRound); }
@@ -2204,6 +2211,12 @@ static int cohort_server_close_dispatch(const float* params, float* global_param
                                         unsigned long long* round_word, float* scale, float* norm, int opt, float b1,
                                         float b2, float tau, float* m, float* v, hipStream_t stream);
 
+// The split close (server_delta != nullptr): cohort_delta_scale_kernel + cohort_delta_kernel, defined at the end of the
+// file behind the server optimizers' kernels.
+static int cohort_delta_close_dispatch(const float* params, const float* global_params, int P, int M, float clip,
+                                       float sigma, unsigned long long seed, unsigned long long* round_word,
+                                       float* scale, float* norm, float* delta, hipStream_t stream);
+
 static int check_cohort_round(const EcgTinyCohortRound* r) {
   if (!r || r->steps < 1 || r->M < 1 || r->M > 65535) return ecg::kBadArg;  // (M is the grid's y extent)
   if (!r->X || !r->Y || !r->idx || !r->params || !r->slab || !r->global_params) return ecg::kBadArg;
@@ -2219,6 +2232,7 @@ static int check_cohort_round(const EcgTinyCohortRound* r) {
   if (r->cdp_clip < 0.f || r->cdp_sigma < 0.f || r->server_lr < 0.f) return ecg::kBadArg;
   if (r->cdp_sigma > 0.f && r->cdp_clip == 0.f) return ecg::kBadArg;
   if (cohort_dp_on(*r) && (!r->cdp_scale || !r->cdp_norm || !r->cdp_round)) return ecg::kBadArg;
+  if (r->server_delta) return (!r->cdp_scale || !r->cdp_norm || !r->cdp_round) ? ecg::kBadArg : ecg::kOk;
   if (r->server_opt != 0)
     return check_server_opt(r->server_opt, r->server_beta1, r->server_beta2, r->server_tau, r->server_m, r->server_v);
   return ecg::kOk;
@@ -2250,6 +2264,9 @@ static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream)
                                 r.nesterov, wprep, stream, gather_next ? &ga : nullptr);
     if (st) return st;
   }
+  if (r.server_delta)
+    return cohort_delta_close_dispatch(r.params, r.global_params, P, r.M, r.cdp_clip, r.cdp_sigma, r.cdp_seed,
+                                       r.cdp_round, r.cdp_scale, r.cdp_norm, r.server_delta, stream);
   if (r.server_opt != 0)
     return cohort_server_close_dispatch(r.params, r.global_params, P, r.M, r.cdp_clip, r.cdp_sigma, r.server_lr,
                                         r.cdp_seed, r.cdp_round, r.cdp_scale, r.cdp_norm, r.server_opt, r.server_beta1,
@@ -2432,4 +2449,131 @@ ECG_API int ecg_cohort_server_close(const float* params, float* global, int nc, 
   if (clip < 0.f || sigma < 0.f || server_lr < 0.f || (sigma > 0.f && clip == 0.f)) return ecg::kBadArg;
   return cohort_server_close_dispatch(params, global, make_layout(nc).P, M, clip, sigma, server_lr, seed, round_word,
                                       scale, norm, opt, b1, b2, tau, m, v, stream);
+}
+
+// ---------------------------------------------------------------------------- the split close (global server step)
+// The closes above take the server step on this rank's delta.  A driver of several ranks that wants ONE server
+// optimizer over all their clients must average the deltas first (the adaptive rules are nonlinear in Delta), so the
+// close is split where Delta exists: cohort_delta_kernel ends the round with Delta in a buffer of its own, the caller
+// all-reduces that buffer, and server_step_kernel takes the step every rank then takes alike.  Run back to back on one
+// rank the pair leaves the bits of the fused close.  (Defined and first named here, behind every older kernel.)
+namespace {
+
+// delta[i] = Delta_i, bit for bit the value cohort_dp_mean_kernel and cohort_server_opt_kernel form (the fused
+// multiply-adds written out, as in the latter and for the reason given there); nothing else is written, and exactly P
+// floats of a client are read.
+template <int NT>
+__global__ __launch_bounds__(NT) void cohort_delta_kernel(
+    const float* __restrict__ params, const float* __restrict__ global_params, int P, int M, float inv_M,
+    const float* __restrict__ scale, float noise_scale, unsigned long long seed,
+    const unsigned long long* __restrict__ round_word, float* __restrict__ delta) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= P) return;
+  const int pstride = cohort_pstride(P);
+  float noise = 0.f;
+  if (noise_scale != 0.f) noise = noise_scale * cohort_dp_normal(i, seed, round_word[0] - 1ull);
+  const float g = global_params[i];
+  float s = scale[0] * (params[i] - g);
+  for (int c = 1; c < M; ++c) s = __builtin_fmaf(scale[c], params[(long)c * pstride + i] - g, s);
+  delta[i] = __builtin_fmaf(s, inv_M, noise);
+}
+
+// One server step on a flat vector of n floats: OPT 0 the plain step g = fma(eta, delta, g) (m and v not touched), OPT
+// 1..4 cohort_server_opt_kernel's rules from Delta on.  Every rounding is pinned - contraction is off in the body and
+// the fused multiply-adds are written out - to what cohort_dp_mean_kernel and cohort_server_opt_kernel compile to, so
+// that the split close ends on their bits: sgdm's two fused multiply-adds, adagrad's v = fma(Delta, Delta, v), yogi's
+// sign taken of fma(-Delta, Delta, v), every other product and sum rounded on its own.  Division and sqrtf are
+// correctly rounded; one thread per element, no atomics.
+template <int NT, int OPT>
+__global__ __launch_bounds__(NT) void server_step_kernel(float* __restrict__ g, const float* __restrict__ delta, long n,
+                                                         float eta, float b1, float b2, float tau,
+                                                         float* __restrict__ m, float* __restrict__ v) {
+#pragma clang fp contract(off)
+  const long i = (long)blockIdx.x * NT + threadIdx.x;
+  if (i >= n) return;
+  const float d = delta[i], g0 = g[i];
+  if (OPT == 0) {
+    g[i] = __builtin_fmaf(eta, d, g0);
+    return;
+  }
+  const float m0 = m[i];
+  float m1;
+  if (OPT == SOPT_SGDM) {
+    m1 = __builtin_fmaf(b1, m0, d);
+    g[i] = __builtin_fmaf(eta, m1, g0);
+  } else {
+    float v1 = v[i];
+    m1 = b1 * m0 + (1.f - b1) * d;
+    if (OPT == SOPT_ADAGRAD) {
+      v1 = __builtin_fmaf(d, d, v1);
+    } else if (OPT == SOPT_ADAM) {
+      v1 = b2 * v1 + (1.f - b2) * (d * d);
+    } else {
+      const float e = __builtin_fmaf(-d, d, v1);
+      const float sg = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
+      v1 = v1 - ((1.f - b2) * (d * d)) * sg;
+    }
+    v[i] = v1;
+    g[i] = g0 + (eta * m1) / (sqrtf(v1) + tau);
+  }
+  m[i] = m1;
+}
+
+}  // namespace
+
+// The two launches of the split close: cohort_delta_scale_kernel as in the other closes (it advances the round word
+// and reports the norms and factors), then cohort_delta_kernel.  clip, sigma and nu as at cohort_dp_close_dispatch.
+static int cohort_delta_close_dispatch(const float* params, const float* global_params, int P, int M, float clip,
+                                       float sigma, unsigned long long seed, unsigned long long* round_word,
+                                       float* scale, float* norm, float* delta, hipStream_t stream) {
+  const float nu = (float)((double)sigma * (double)clip / (double)M);
+  hipLaunchKernelGGL(cohort_delta_scale_kernel<CDP_CLIENTS_PER_BLOCK>,
+                     dim3((M + CDP_CLIENTS_PER_BLOCK - 1) / CDP_CLIENTS_PER_BLOCK), dim3(CDP_CLIENTS_PER_BLOCK * 64), 0,
+                     stream, params, global_params, P, M, clip > 0.f ? clip : FLT_MAX, scale, norm, round_word);
+  ECG_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(cohort_delta_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, params, global_params, P, M,
+                     1.0f / (float)M, (const float*)scale, nu, seed, (const unsigned long long*)round_word, delta);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+// ecg_cohort_dp_close's twin that stops at the delta: the same buffers and meaning of clip, sigma, seed and the round
+// word; ``global`` [P] is only read, ``delta`` [P] receives the averaged, clipped, noised delta.
+ECG_API int ecg_cohort_delta_close(const float* params, const float* global, int nc, int M, float clip, float sigma,
+                                   unsigned long long seed, unsigned long long* round_word, float* scale, float* norm,
+                                   float* delta, hipStream_t stream) {
+  if (!params || !global || !round_word || !scale || !norm || !delta || nc < 1 || nc > MAX_CLASSES)
+    return ecg::kBadArg;
+  if (M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
+  if (clip < 0.f || sigma < 0.f || (sigma > 0.f && clip == 0.f)) return ecg::kBadArg;
+  return cohort_delta_close_dispatch(params, global, make_layout(nc).P, M, clip, sigma, seed, round_word, scale, norm,
+                                     delta, stream);
+}
+
+// One server step on ``g`` [n] from ``delta`` [n] (the second half of the split close, after the caller averaged the
+// ranks' deltas): ``opt`` 0 the plain step g += eta delta (m and v are not read and may be null), 1 sgdm, 2 adagrad, 3
+// adam, 4 yogi with the server state ``m`` / ``v`` [n], read and written (``v`` may be null for sgdm); eta == 0 means
+// 1; beta1, beta2 in [0, 1) and tau > 0 as in check_server_opt.
+ECG_API int ecg_server_opt_step(float* g, const float* delta, long n, int opt, float eta, float b1, float b2, float tau,
+                                float* m, float* v, hipStream_t stream) {
+  if (!g || !delta || n < 1 || eta < 0.f) return ecg::kBadArg;
+  if (opt != 0) {
+    const int st = check_server_opt(opt, b1, b2, tau, m, v);
+    if (st) return st;
+  }
+  if ((n + 255) / 256 > (long)INT_MAX) return ecg::kTooLarge;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  const float step = eta == 0.f ? 1.f : eta;
+#define ECG_SERVER_STEP_LAUNCH(OPT) \
+  hipLaunchKernelGGL((server_step_kernel<256, OPT>), grid, block, 0, stream, g, delta, n, step, b1, b2, tau, m, v)
+  switch (opt) {
+    case 0: ECG_SERVER_STEP_LAUNCH(0); break;
+    case SOPT_SGDM: ECG_SERVER_STEP_LAUNCH(SOPT_SGDM); break;
+    case SOPT_ADAGRAD: ECG_SERVER_STEP_LAUNCH(SOPT_ADAGRAD); break;
+    case SOPT_ADAM: ECG_SERVER_STEP_LAUNCH(SOPT_ADAM); break;
+    default: ECG_SERVER_STEP_LAUNCH(SOPT_YOGI); break;
+  }
+#undef ECG_SERVER_STEP_LAUNCH
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
 }

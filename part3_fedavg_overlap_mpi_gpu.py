@@ -21,7 +21,10 @@ mean, server step size eta; cumulative client-level epsilon per round at sample 
 bound as an approximation; avg_loss and the evaluation metrics are not private)
 --server-opt {none,sgdm,adagrad,adam,yogi} --server-beta1 b1 --server-beta2 b2 --server-tau tau (server optimizer on a
 cohort round's averaged client delta with step size --server-lr, needs --clients-per-gpu: FedAvgM, FedAdagrad, FedAdam,
-FedYogi; state kept in the per-rank checkpoint; the three adaptive ones not under --sync fedavg on more than one rank)
+FedYogi; state kept in the per-rank checkpoint; the three adaptive ones under --sync fedavg on more than one rank only
+with --server-scope global)
+--server-scope {rank,global} (global, needs --clients-per-gpu: the ranks' cohort deltas are all-reduced in place of
+their weights and every rank takes one replicated server step on the average - a global server optimizer)
 """
 from __future__ import annotations
 
