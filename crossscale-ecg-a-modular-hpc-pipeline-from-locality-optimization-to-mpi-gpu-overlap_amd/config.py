@@ -78,6 +78,13 @@ class FedAvgConfig:
     # all-reduce of the ranks' deltas, one replicated step on every rank (what adagrad, adam and yogi need under
     # sync fedavg on more than one rank)
     server_scope: str = "rank"
+    # FedProx (off by default; TinyECG on the fused backend with or without client sampling, any model on the torch
+    # backend): every local step's gradient gains prox_mu * (w - the weights the round started from)
+    prox_mu: float = 0.0
+    # how a GPU's training windows are dealt to its virtual clients (needs clients_per_gpu > 1): contiguous slices, or
+    # "shards" - client_shards runs of the label-sorted windows per client (label-skewed, non-IID clients)
+    client_partition: str = "contiguous"
+    client_shards: int = 2
     results_csv: str = "results/fedavg_results.csv"
     jsonl: Optional[str] = None
     model: str = "tiny_ecg"

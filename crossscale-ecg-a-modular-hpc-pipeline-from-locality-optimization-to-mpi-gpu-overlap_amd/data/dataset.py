@@ -260,6 +260,45 @@ class DeviceIndexSampler:
         return self.fill(t)[0]
 
 
+PARTITIONS = ("contiguous", "shards")
+
+
+def shard_partition(y: torch.Tensor, clients: int, shards_per_client: int, seed: Optional[int]) -> torch.Tensor:
+    """Label-skewed clients, the sort-and-deal partition of McMahan et al. ("Communication-Efficient Learning of Deep
+    Networks from Decentralized Data"): int64 ``[K, n]`` on ``y``'s device, row k the dataset rows of client k.
+
+    The stable argsort of the labels ``y`` [N] is cut into ``K * s`` shards of ``n / s`` consecutive entries, with
+    ``n = s * (N // (K * s))`` (a remainder at the end of the sorted order is unused), and the shards are dealt by a host
+    permutation seeded from ``mix64(seed)``: client k owns shards ``perm[k * s : (k + 1) * s]``, so its rows come from at
+    most s runs of the sorted order - with two classes and s = 2 most clients see one or two labels.  A pure function
+    of its arguments: a resumed run rebuilds the partition it had."""
+    from ..utils.philox import mix64
+    K, s = int(clients), int(shards_per_client)
+    if K < 1 or s < 1:
+        raise ValueError(f"need clients >= 1 and shards_per_client >= 1, got {K} and {s}")
+    if y.dim() != 1:
+        raise ValueError("labels must be a vector [N]")
+    rows = y.shape[0] // (K * s)  # rows of one shard
+    if rows < 1:
+        raise RuntimeError(f"{y.shape[0]} windows are fewer than {K} clients x {s} shards")
+    order = torch.argsort(y, stable=True)[: K * s * rows].view(K * s, rows)
+    g = torch.Generator()
+    g.manual_seed(mix64(0 if seed is None else int(seed)) & ((1 << 63) - 1))
+    perm = torch.randperm(K * s, generator=g).to(order.device)
+    return order[perm].reshape(K, s * rows).to(torch.int64).contiguous()
+
+
+def client_partition(partition: str, y: torch.Tensor, clients: int, shards_per_client: int, seed: Optional[int],
+                     device) -> Optional[torch.Tensor]:
+    """The ``order`` argument of ``CohortSampler`` for a trainer's ``partition``: None for "contiguous" (client k owns
+    rows ``[k * n, (k + 1) * n)``), ``shard_partition`` of the labels on ``device`` for "shards"."""
+    if partition not in PARTITIONS:
+        raise ValueError(f"partition must be one of {list(PARTITIONS)}, got {partition!r}")
+    if partition == "contiguous":
+        return None
+    return shard_partition(y, clients, shards_per_client, seed).to(device)
+
+
 class CohortSampler:
     """Client sampling for cohorts of virtual clients: which clients train in round ``r``, and on which rows.
 
@@ -272,18 +311,29 @@ class CohortSampler:
     the same pair.  ``fill`` writes them as the table ``[steps][cohort * B]``, client j of the cohort in columns
     ``[j * B, (j + 1) * B)``.
 
+    ``order`` (int64 ``[clients, n]``, e.g. ``shard_partition``): client k's local row j is dataset row ``order[k, j]``
+    instead of ``k * n + j``, and ``n`` is its row length; None: the contiguous partitions, the tables of before.
+
     The sampler holds no state between rounds: a run resumed at round r draws what the uninterrupted run drew.
     """
 
     def __init__(self, n_windows: int, batch_size: int, steps: int, clients: int, cohort: int, device,
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None, order: Optional[torch.Tensor] = None):
         if clients < 1 or not 1 <= cohort <= clients:
             raise ValueError(f"need 1 <= cohort <= clients, got cohort {cohort} of {clients} clients")
         self.N, self.B, self.S, self.K, self.M = int(n_windows), int(batch_size), int(steps), int(clients), int(cohort)
         self.n = self.N // self.K
+        self.device = torch.device(device)
+        self.order = None
+        if order is not None:
+            if order.dim() != 2 or order.shape[0] != self.K or order.dtype != torch.int64:
+                raise ValueError(f"order must be int64 [{self.K}, n], got {order.dtype} {tuple(order.shape)}")
+            if order.numel() and (int(order.min()) < 0 or int(order.max()) >= self.N):
+                raise ValueError(f"order holds rows outside [0, {self.N})")
+            self.order = order.to(self.device)
+            self.n = int(order.shape[1])
         if self.n < self.B:
             raise RuntimeError(f"{self.N} windows over {self.K} clients leave {self.n} per client < batch {self.B}")
-        self.device = torch.device(device)
         self.seed = 0 if seed is None else int(seed)
         self.passes = (self.S * self.B + self.n - 1) // self.n  # permutations of a partition per client and round
 
@@ -309,7 +359,10 @@ class CohortSampler:
         keys = torch.randint(0, 1 << 62, (self.M, self.passes, self.n), device=self.device, generator=g,
                              dtype=torch.int64)
         rows = keys.argsort(dim=2).reshape(self.M, self.passes * self.n)[:, : self.S * self.B]
-        rows = rows + (torch.tensor(ids, dtype=torch.int64) * self.n).to(self.device)[:, None]
+        if self.order is None:
+            rows = rows + (torch.tensor(ids, dtype=torch.int64) * self.n).to(self.device)[:, None]
+        else:
+            rows = self.order[torch.tensor(ids, dtype=torch.int64).to(self.device)].gather(1, rows)
         # [M, S, B] -> [S, M, B]: a step's row holds the clients' batches back to back
         table.copy_(rows.view(self.M, self.S, self.B).permute(1, 0, 2).reshape(self.S, self.M * self.B))
         return ids

@@ -67,7 +67,8 @@ class TinyRound(C.Structure):
                 ("L", i32), ("nc", i32), ("slab_stride", i32), ("B", i32), ("steps", i32),
                 ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32),
                 ("dp_clip", f32), ("dp_sigma", f32), ("dp_seed", u64), ("dp_scale", vp), ("dp_step", vp),
-                ("xbg", vp), ("xpk", vp), ("prepack", i32)]
+                ("xbg", vp), ("xpk", vp), ("prepack", i32),
+                ("prox_mu", f32), ("prox_anchor", vp), ("prox_snapshot", i32)]
 
 
 PREPACK = {"none": 0, "gather": 1, "direct": 2}  # kPrepack* of csrc/kernels/tiny_ecg_step.hip (TinyRound.prepack)
@@ -81,7 +82,8 @@ class TinyCohortRound(C.Structure):
                 ("fanout", i32), ("lr", f32), ("momentum", f32), ("wd", f32), ("nesterov", i32), ("prec", i32),
                 ("cdp_clip", f32), ("cdp_sigma", f32), ("server_lr", f32), ("cdp_seed", u64), ("cdp_scale", vp),
                 ("cdp_norm", vp), ("cdp_round", vp), ("server_opt", i32), ("server_beta1", f32), ("server_beta2", f32),
-                ("server_tau", f32), ("server_m", vp), ("server_v", vp), ("server_delta", vp)]
+                ("server_tau", f32), ("server_m", vp), ("server_v", vp), ("server_delta", vp),
+                ("prox_mu", f32)]
 
 
 def _bind_kernels(lib: C.CDLL) -> None:
@@ -98,6 +100,9 @@ def _bind_kernels(lib: C.CDLL) -> None:
     _sig(lib, "ecg_slab_reduce_dp_sgd", [vp, i32, i32, i32, vp, vp, vp, vp, f32, f32, f32, i32, i32, vp,
                                          f32, f32, u64, vp, vp, vp])
     _sig(lib, "ecg_dp_noise", [vp, i32, u64, u64, vp])
+    _sig(lib, "ecg_slab_reduce_prox_sgd", [vp, i32, i32, i32, vp, vp, vp, vp, f32, f32, f32, i32, i32, vp, vp, f32, vp])
+    _sig(lib, "ecg_slab_reduce_cohort_prox_sgd", [vp, i32, i32, i32, i32, vp, vp, vp, f32, f32, f32, i32, vp, vp, f32,
+                                                  vp])
     native = _sig(lib, "ecg_tiny_round_sizeof", [])()
     if native != C.sizeof(TinyRound):
         raise NativeError(f"EcgTinyRound is {native} bytes in libecg_kernels.so but {C.sizeof(TinyRound)} in "

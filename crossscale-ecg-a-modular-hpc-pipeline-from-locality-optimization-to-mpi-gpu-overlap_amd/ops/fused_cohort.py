@@ -26,6 +26,13 @@ which leave this rank's averaged, clipped, noised delta in ``server_delta`` ([P]
 untouched; the driver all-reduces ``server_delta`` and ``apply_server_step`` (``server_step_kernel``) then takes the
 step - the plain one for ``server_opt="none"`` - on every rank alike.  On one rank the two halves leave the bits of the
 default ``server_scope="rank"``.
+
+FedProx (``prox_mu`` > 0): every client's local steps add ``prox_mu * (w - g)`` to the gradient, g the global weights the
+round started from (``slab_reduce_cohort_prox_sgd_kernel``).  The anchor is the global weight buffer itself: the fan-out
+leaves g there and no launch writes it before the close, so the round needs no copy and no further buffer.
+
+``partition="shards"`` deals the clients label-skewed partitions (``data.dataset.shard_partition``: ``shards_per_client``
+runs of the label-sorted windows each) instead of contiguous slices of the windows.
 """
 from __future__ import annotations
 
@@ -36,7 +43,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from ..data.dataset import CohortSampler
+from ..data.dataset import CohortSampler, client_partition
 from ..models.tiny_ecg import TinyECG, num_params
 from .fused_tiny import _check_dataset, labels_int32, prec_id, slab_stride
 from .tiny_eval import EvalResult, TinyEvaluator, tiny_evaluate
@@ -54,7 +61,10 @@ class FusedCohortTrainer:
                  use_graph: Optional[bool] = None, precision: str = "bf16", dp_clip: float = 0.0,
                  client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
                  server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
-                 server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank"):
+                 server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank",
+                 prox_mu: float = 0.0, partition: str = "contiguous", shards_per_client: int = 2):
+        if not prox_mu >= 0.0:
+            raise ValueError(f"prox_mu must be >= 0, got {prox_mu}")
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients: the cohort "
                              "reduce has no per-sample clip")
@@ -77,7 +87,11 @@ class FusedCohortTrainer:
         self.K = int(clients)
         self.M = self.K if not cohort else int(cohort)
         self.lr, self.momentum, self.wd, self.nesterov = float(lr), float(momentum), float(weight_decay), bool(nesterov)
-        self.sampler = CohortSampler(self.x.shape[0], self.B, self.S, self.K, self.M, self.device, seed=seed)
+        self.partition, self.shards_per_client = partition, int(shards_per_client)
+        order = client_partition(partition, y_gpu, self.K, self.shards_per_client, seed, self.device)
+        self.sampler = CohortSampler(self.x.shape[0], self.B, self.S, self.K, self.M, self.device, seed=seed,
+                                     order=order)
+        self.prox_mu = float(prox_mu)
         lib = _lib.kernels()
         L = self.x.shape[1]
         if lib.ecg_tiny_smem_bytes(L, self.prec) > 160 * 1024:
@@ -132,7 +146,8 @@ class FusedCohortTrainer:
             mom=self.cmom.data_ptr(), slab=self.slab.data_ptr(), loss_acc=self.loss_acc.data_ptr(),
             wprep=_lib.ptr(self.wprep), xg=_lib.ptr(self.xg), yg=_lib.ptr(self.yg), xbg=_lib.ptr(self.xbg),
             global_params=self.params.data_ptr(), L=L, nc=self.nc, slab_stride=self.stride, B=self.B, M=self.M,
-            fanout=1, lr=self.lr, momentum=self.momentum, wd=self.wd, nesterov=int(self.nesterov), prec=self.prec)
+            fanout=1, lr=self.lr, momentum=self.momentum, wd=self.wd, nesterov=int(self.nesterov), prec=self.prec,
+            prox_mu=self.prox_mu)
         if self.client_dp:  # (all-zero fields otherwise: the round then issues the launches it always issued)
             r = self._round
             r.cdp_clip, r.cdp_sigma = self.cdp_clip, client_dp_sigma_share(self.cdp_noise, world_size)

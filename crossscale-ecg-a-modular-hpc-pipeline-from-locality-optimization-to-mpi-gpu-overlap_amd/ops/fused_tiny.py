@@ -165,6 +165,14 @@ def check_dp_args(dp_clip: float, dp_noise: float) -> None:
         raise ValueError("dp_noise > 0 needs a clip norm (dp_clip > 0): the noise is scaled by it")
 
 
+def check_prox_args(prox_mu: float, dp_clip: float = 0.0) -> None:
+    if not prox_mu >= 0.0:
+        raise ValueError(f"prox_mu must be >= 0, got {prox_mu}")
+    if prox_mu > 0.0 and dp_clip > 0.0:
+        raise ValueError("FedProx (prox_mu > 0) is not combined with DP-SGD (dp_clip > 0): the DP reduce has no "
+                         "proximal term")
+
+
 def dp_reduce_slab(slab: torch.Tensor, dp_clip: float, dp_noise: float, dp_seed: int, dp_step: torch.Tensor,
                    num_classes: int = 2):
     """DP-SGD sum of a gradient slab without an update: returns (grad [P], loss_sum [1], clip factors [B]) where
@@ -243,6 +251,13 @@ class FusedTinyTrainer:
     (``utils/philox.py``) keyed by ``dp_seed`` (default: a mix of ``seed``) and a 64-bit step counter kept on the
     device (``dp_step``; host mirror ``dp_steps``), so graph replays, enqueued rounds and the torch backend draw the
     same values.  The training loss is summed unclipped and un-noised: it is not private.
+
+    FedProx (``prox_mu`` > 0; Li et al., "Federated Optimization in Heterogeneous Networks"): the local objective gains
+    ``prox_mu / 2 * |w - w_start|^2``, ``w_start`` the weights the round started from, so every step's gradient gains
+    ``prox_mu * (w - w_start)`` in the reduce kernel's SGD epilogue (``slab_reduce_prox_sgd_kernel``; it passes through
+    momentum like any other gradient).  The round's first launch copies the weights into ``prox_anchor``, a tensor this
+    trainer owns and only ever writes in place (captured graphs hold its address), so a replayed graph re-anchors every
+    round and there is no state to save.  Not combined with DP-SGD.  ``prox_mu == 0``: the launches of before.
     """
 
     def __init__(self, model: TinyECG, x_gpu: torch.Tensor, y_gpu: torch.Tensor, batch_size: int,
@@ -251,7 +266,8 @@ class FusedTinyTrainer:
                  precision: str = "bf16", prefrag: bool = True, gather: Optional[bool] = None,
                  pack: Optional[bool] = None,
                  prepack=None, prepack_share: float = PREPACK_SHARE,
-                 dp_clip: float = 0.0, dp_noise: float = 0.0, dp_seed: Optional[int] = None):
+                 dp_clip: float = 0.0, dp_noise: float = 0.0, dp_seed: Optional[int] = None, prox_mu: float = 0.0):
+        check_prox_args(prox_mu, dp_clip)
         self.device = x_gpu.device
         self.precision = precision
         self.prec = prec_id(precision)
@@ -315,6 +331,8 @@ class FusedTinyTrainer:
         if self.dp:
             self.dp_scale = torch.zeros(self.B, dtype=torch.float32, device=self.device)
             self.dp_step = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.prox_mu = float(prox_mu)
+        self.prox_anchor = torch.zeros_like(self.params) if self.prox_mu > 0.0 else None
         # the native description of a round; ``idx`` and ``steps`` are set per round (_round_of)
         self._round = _lib.TinyRound(
             X=self.x.data_ptr(), ldx=self.x.stride(0), Y=self.y32.data_ptr(), params=self.params.data_ptr(),
@@ -324,6 +342,9 @@ class FusedTinyTrainer:
             nesterov=int(self.nesterov), prec=self.prec, dp_clip=self.dp_clip, dp_sigma=self.dp_noise,
             dp_seed=self.dp_seed, dp_scale=_lib.ptr(self.dp_scale), dp_step=_lib.ptr(self.dp_step),
             xbg=_lib.ptr(self.xbg), xpk=_lib.ptr(self.xpk), prepack=_lib.PREPACK[self.prepack])
+        if self.prox_mu > 0.0:  # (all-zero fields otherwise: the round then issues the launches it always issued)
+            r = self._round
+            r.prox_mu, r.prox_anchor, r.prox_snapshot = self.prox_mu, self.prox_anchor.data_ptr(), 1
 
     def _alloc_prepacked(self) -> None:
         """Allocate and fill the packed shard, or record why not and keep the unpacked path."""

@@ -24,6 +24,11 @@ bracket above - Delta, the averaged, clipped, noised delta - as its pseudo-gradi
 ``server_scope="global"`` takes the same two phases apart: ``launch_round`` ends with Delta in ``server_delta`` (a
 tensor written in place) and the model untouched, and ``apply_server_step`` takes the plain step or the optimizer's on
 whatever ``server_delta`` then holds - the mean of the ranks' Deltas once a driver all-reduced it.
+
+FedProx (``prox_mu`` mu > 0): every client's local objective gains ``mu / 2 * |w - g|^2``, g the global weights the
+round started from: after ``backward()`` every ``p.grad`` gains ``mu * (p - g)`` in fp32, before ``opt.step()`` - the
+definition ``slab_reduce_cohort_prox_sgd_kernel`` implements.  ``partition="shards"``: label-skewed clients
+(``data.dataset.shard_partition``).
 """
 from __future__ import annotations
 
@@ -35,8 +40,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..data.dataset import CohortSampler
+from ..data.dataset import CohortSampler, client_partition
 from ..utils import philox
+from .local import add_prox_grad, check_prox
 from .server_opt import (BETA1, BETA2, TAU, check_server_opt, check_server_scope, server_opt_init,
                          server_opt_step)
 
@@ -48,7 +54,10 @@ class TorchCohortTrainer:
                  amp_dtype: Optional[torch.dtype] = None, seed: Optional[int] = None, dp_clip: float = 0.0,
                  client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
                  server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
-                 server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank"):
+                 server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank",
+                 prox_mu: float = 0.0, partition: str = "contiguous", shards_per_client: int = 2):
+        check_prox(prox_mu, amp_dtype, model)
+        self.prox_mu = float(prox_mu)
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients")
         check_client_dp(client_dp_clip, client_dp_noise, server_lr, world_size)
@@ -60,7 +69,9 @@ class TorchCohortTrainer:
         self.M = self.K if not cohort else int(cohort)
         self.opt_args = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
         self.amp_dtype = amp_dtype
-        self.sampler = CohortSampler(x.shape[0], self.B, self.S, self.K, self.M, self.device, seed=seed)
+        self.partition, self.shards_per_client = partition, int(shards_per_client)
+        order = client_partition(partition, y, self.K, self.shards_per_client, seed, self.device)
+        self.sampler = CohortSampler(x.shape[0], self.B, self.S, self.K, self.M, self.device, seed=seed, order=order)
         self.table = torch.zeros((self.S, self.M * self.B), dtype=torch.int32, device=self.device)
         self.work = copy.deepcopy(model)  # one client's model: reloaded from the global weights per client
         if getattr(self.work, "_flat", None) is not None:
@@ -112,6 +123,8 @@ class TorchCohortTrainer:
             with torch.autocast(device_type=self.device.type, dtype=self.amp_dtype or torch.float32, enabled=use_amp):
                 loss = F.cross_entropy(self.work(xb), yb)
             loss.backward()
+            if self.prox_mu > 0.0:
+                add_prox_grad(self.work.parameters(), self.model.parameters(), self.prox_mu)
             opt.step()
             self.loss_acc += loss.detach().float()
         return [p.detach().clone() for p in self.work.parameters()]

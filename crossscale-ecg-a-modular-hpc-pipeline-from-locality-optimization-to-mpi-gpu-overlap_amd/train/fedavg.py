@@ -67,6 +67,16 @@ MI355X execution (vs the reference's host-staged per-tensor MPI calls and per-st
     optimizer state stay replicated, all five rules are exact, and m / v are global.  The mean of W deltas that each
     carry a sigma / sqrt(W) noise share has the noise the accountant assumes.  Without a collective (one rank,
     ``--sync none``) the step follows the round at once and ends on the bits of ``rank``.
+  * ``--prox-mu mu``: FedProx local steps.  The local objective gains ``mu / 2 * |w - w_start|^2``, ``w_start`` the weights
+    the local round started from - the averaged model; for a virtual client the round's global weights - so every step's
+    gradient gains ``mu * (w - w_start)`` and passes through momentum like any other gradient.  TinyECG on the fused
+    backend (in the reduce kernel's SGD epilogue, with or without ``--clients-per-gpu``) and any model on the torch
+    backend; it composes with the server optimizers, client-level DP and ``--server-scope global``.  Not combined with
+    ``--dp-clip``, ``--sync ddp``, fp16 AMP, the ResNet1D engine or ``--overlap delayed``.
+  * ``--client-partition {contiguous,shards}`` / ``--client-shards s`` (need ``--clients-per-gpu``): with ``shards``
+    every GPU's training windows are sorted by label, cut into K * s shards and dealt s to a virtual client
+    (``data.dataset.shard_partition``, a function of the labels, K, s and ``seed + 7919 * rank``): label-skewed clients.
+    A ``prox`` event in ``--jsonl`` records mu, the partition and s; no CSV and no checkpoint changes.
 """
 from __future__ import annotations
 
@@ -200,6 +210,38 @@ def check_dp_config(cfg: FedAvgConfig, config_name: str, backend: str) -> None:
             if backend == "fused" else "per-sample gradients bypass DistributedDataParallel's gradient hooks"))
 
 
+def check_prox_config(cfg: FedAvgConfig, config_name: str, backend: str) -> None:
+    """FedProx exists for TinyECG on the fused backend and for any model on the torch backend, with local rounds that
+    start from the averaged model; a client partition other than the contiguous one needs client sampling."""
+    from ..data.dataset import PARTITIONS
+    if not cfg.prox_mu >= 0:
+        raise ValueError("--prox-mu must be >= 0")
+    if cfg.client_partition not in PARTITIONS:
+        raise ValueError(f"--client-partition must be one of {list(PARTITIONS)}, got {cfg.client_partition!r}")
+    if cfg.client_shards < 1:
+        raise ValueError("--client-shards must be >= 1")
+    if (cfg.client_partition != "contiguous" or cfg.client_shards != 2) and cfg.clients_per_gpu <= 1:
+        raise ValueError("--client-partition / --client-shards need client sampling (--clients-per-gpu K > 1): they "
+                         "deal a GPU's windows to its virtual clients")
+    if cfg.prox_mu == 0:
+        return
+    if backend == "hip":
+        raise ValueError("FedProx (--prox-mu) is implemented for TinyECG on the fused backend and for the torch backend, "
+                         "not for the ResNet1D engine (--kernel-backend hip)")
+    if cfg.sync == "ddp":
+        raise ValueError("FedProx (--prox-mu) does not support --sync ddp: its per-step gradient all-reduce bypasses "
+                         "the round, and with it the round's starting weights that the proximal term pulls towards")
+    if cfg.dp_clip > 0:
+        raise ValueError("FedProx (--prox-mu) does not support DP-SGD (--dp-clip): the proximal gradient is not part "
+                         "of the clipped per-sample gradients, and the DP reduce has no proximal term")
+    if config_name == "G1" and cfg.amp_dtype == "fp16":
+        raise ValueError("FedProx (--prox-mu) does not support fp16 AMP: its GradScaler would rescale the proximal "
+                         "gradient; use --amp-dtype bf16 or none")
+    if cfg.overlap == "delayed":
+        raise ValueError("FedProx (--prox-mu) does not support --overlap delayed: a round there starts before the "
+                         "averaged model exists, so its starting weights are not the anchor FedProx defines")
+
+
 def cohort_size(cfg: FedAvgConfig) -> int:
     """Clients trained per GPU and round: 1 without client sampling, else ``--cohort`` (default: all K)."""
     if cfg.clients_per_gpu <= 1:
@@ -288,8 +330,10 @@ def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistCont
     check_cohort_config(cfg, backend)
     check_client_dp_config(cfg)
     check_server_opt_config(cfg, ctx)
+    check_prox_config(cfg, config_name, backend)
     if cfg.clients_per_gpu > 1:
-        kw = dict(clients=cfg.clients_per_gpu, cohort=cohort_size(cfg), lr=cfg.lr, momentum=cfg.momentum, seed=seed,
+        kw = dict(prox_mu=cfg.prox_mu, partition=cfg.client_partition, shards_per_client=cfg.client_shards,
+                  clients=cfg.clients_per_gpu, cohort=cohort_size(cfg), lr=cfg.lr, momentum=cfg.momentum, seed=seed,
                   client_dp_clip=cfg.client_dp_clip, client_dp_noise=cfg.client_dp_noise, client_dp_seed=mix64(seed),
                   server_lr=cfg.server_lr, world_size=client_dp_world(cfg, ctx), server_opt=cfg.server_opt,
                   server_beta1=cfg.server_beta1, server_beta2=cfg.server_beta2, server_tau=cfg.server_tau,
@@ -308,7 +352,7 @@ def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistCont
         from ..ops.fused_tiny import FusedTinyTrainer
         prec = "bf16" if (config_name == "G1" and cfg.amp_dtype == "bf16") else "fp32"
         return FusedTinyTrainer(model, x, y, cfg.batch_size, cfg.local_steps, lr=cfg.lr, momentum=cfg.momentum,
-                                seed=seed, precision=prec, **dp)
+                                seed=seed, precision=prec, prox_mu=cfg.prox_mu, **dp)
     if backend == "hip":  # ResNet1D on the native step engine
         from .resnet_trainer import ResNetEngineTrainer
         return ResNetEngineTrainer(model, x, y, cfg.batch_size, cfg.local_steps, lr=cfg.lr, momentum=cfg.momentum,
@@ -319,7 +363,7 @@ def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistCont
         from torch.nn.parallel import DistributedDataParallel as DDP
         net = DDP(model, device_ids=[dev_index(ctx)] if ctx.device.type == "cuda" else None, bucket_cap_mb=cfg.bucket_mb)
     return TorchLocalTrainer(net, x, y, cfg.batch_size, lr=cfg.lr, momentum=cfg.momentum, amp_dtype=amp, seed=seed,
-                             **dp)
+                             prox_mu=cfg.prox_mu, **dp)
 
 
 def dev_index(ctx):
@@ -421,6 +465,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
     for cname in configs:  # an unsupported DP-SGD combination stops the run before any configuration trains
         check_dp_config(cfg, cname, pick_backend(cfg, cname, ctx))
         check_cohort_config(cfg, pick_backend(cfg, cname, ctx))
+        check_prox_config(cfg, cname, pick_backend(cfg, cname, ctx))
     check_client_dp_config(cfg)
     check_server_opt_config(cfg, ctx)
     M = cohort_size(cfg)  # clients trained per GPU and round (1: no client sampling)
@@ -438,6 +483,9 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         if cfg.server_opt != "none":
             log.event("server_opt", config=cname, server_opt=cfg.server_opt, server_lr=cfg.server_lr,
                       beta1=cfg.server_beta1, beta2=cfg.server_beta2, tau=cfg.server_tau, scope=cfg.server_scope)
+        if cfg.prox_mu > 0 or cfg.client_partition != "contiguous":
+            log.event("prox", config=cname, mu=cfg.prox_mu, partition=cfg.client_partition,
+                      shards_per_client=cfg.client_shards)
         start_round = _resume(cfg, cname, ctx, comm, model, trainer, log) if cfg.resume else 0
         if hasattr(trainer, "set_cohort_round"):  # the cohort sampler is a function of (seed, round): no other state
             trainer.set_cohort_round(start_round)

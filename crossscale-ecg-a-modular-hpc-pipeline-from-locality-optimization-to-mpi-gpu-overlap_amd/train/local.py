@@ -9,6 +9,11 @@ DP-SGD (``dp_clip`` > 0, the definition of ``FusedTinyTrainer``): per-sample gra
 (``functional_call`` + ``vmap(grad)``), clipped in fp32 to l2 norm ``dp_clip``, summed, plus ``dp_noise * dp_clip * z``
 with ``z`` from ``utils/philox.py`` at (``dp_seed``, step counter), divided by B, then the optimizer's usual update.
 The same seed and counter give the noise the HIP kernels draw.  The reported loss is not private.
+
+FedProx (``prox_mu`` mu > 0): ``run_steps`` / ``run_round`` snapshot the weights ``a`` they start from, and every step
+adds ``mu * (p - a)`` to ``p.grad`` in fp32 after ``backward()`` and before ``opt.step()`` - the gradient of
+``mu / 2 * |w - a|^2`` passed through the optimizer like any other gradient, which is the definition
+``slab_reduce_prox_sgd_kernel`` implements.
 """
 from __future__ import annotations
 
@@ -21,12 +26,34 @@ from ..data.dataset import DeviceIndexSampler
 from ..utils import philox
 
 
+def check_prox(prox_mu: float, amp_dtype, model) -> None:
+    if not prox_mu >= 0.0:
+        raise ValueError(f"prox_mu must be >= 0, got {prox_mu}")
+    if prox_mu > 0.0:
+        if amp_dtype == torch.float16:
+            raise ValueError("FedProx does not support fp16 AMP (a GradScaler would rescale the proximal gradient)")
+        if isinstance(model, torch.nn.parallel.DistributedDataParallel):
+            raise ValueError("FedProx does not support a DistributedDataParallel model (--sync ddp)")
+
+
+def add_prox_grad(params, anchors, mu: float) -> None:
+    """``p.grad += mu * (p - a)`` for every parameter, computed in fp32."""
+    with torch.no_grad():
+        for p, a in zip(params, anchors):
+            p.grad.add_(((p.detach().float() - a.detach().float()) * mu).to(p.grad.dtype))
+
+
 class TorchLocalTrainer:
     def __init__(self, model: torch.nn.Module, x: torch.Tensor, y: torch.Tensor, batch_size: int,
                  lr: float = 1e-2, momentum: float = 0.9, weight_decay: float = 0.0,
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, seed: Optional[int] = None,
                  sync_each_step: bool = False, dp_clip: float = 0.0, dp_noise: float = 0.0,
-                 dp_seed: Optional[int] = None):
+                 dp_seed: Optional[int] = None, prox_mu: float = 0.0):
+        check_prox(prox_mu, amp_dtype, model)
+        if prox_mu > 0.0 and dp_clip > 0.0:
+            raise ValueError("FedProx (prox_mu > 0) is not combined with DP-SGD (dp_clip > 0)")
+        self.prox_mu = float(prox_mu)
+        self._anchor = None  # FedProx: the weights the current round started from (set by run_steps)
         self.model, self.x, self.y, self.B = model, x, y, batch_size
         self.device = x.device
         self.opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=weight_decay)
@@ -106,6 +133,10 @@ class TorchLocalTrainer:
             self.scaler.update()
         else:
             loss.backward()
+            if self.prox_mu > 0.0:
+                if self._anchor is None:  # a step outside run_steps anchors on the weights it finds
+                    self._anchor = [p.detach().clone() for p in self.model.parameters()]
+                add_prox_grad(self.model.parameters(), self._anchor, self.prox_mu)
             self.opt.step()
         if self.sync_each_step and self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
@@ -116,6 +147,8 @@ class TorchLocalTrainer:
         if reset_loss:
             self.loss_acc.zero_()
             self._loss_steps = 0
+        if self.prox_mu > 0.0:
+            self._anchor = [p.detach().clone() for p in self.model.parameters()]
         for _ in range(n):
             self.loss_acc += self.step().float()
         self._loss_steps += n

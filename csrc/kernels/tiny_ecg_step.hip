@@ -1247,11 +1247,17 @@ __device__ inline float dp_normal(int i, unsigned long long seed, unsigned long 
 // scale[b] == 1 and no noise, and a cohort of one, give the plain kernel's bits.  The pointers carry no __restrict__
 // here: the kernels' own parameters do, and a second set of alias scopes from the inlined body changes the gather
 // branch's code (profiles/r12/tiny_reduce_merge.txt).
-template <int RED_COLS, bool DP, bool COHORT>
+// PROX (FedProx, Li et al. 2020): the gradient that enters the epilogue gains mu * (p - anchor[col]), the gradient of
+// mu/2 * |w - anchor|^2: d = gsum + wd * p + mu * (p - a), which then passes through momentum and nesterov like any
+// other gradient (torch.optim.SGD with mu * (p - a) added to p.grad).  ``anchor`` [P] is shared by all clients of a cohort
+// (never offset by the client stride); the updating thread loads it beside p0 / m0, before the slab reads.  The two
+// arguments are trailing defaults: the three older kernels' calls, and their code, stay as they were.
+template <int RED_COLS, bool DP, bool COHORT, bool PROX = false>
 __device__ __forceinline__ void slab_reduce_body(
     const float* slab, float* params, float* mom, int nred, int G, int stride, int P, int flags, float momentum,
     float lr, float wd, unsigned char* wprep, float* loss_acc, float* grad_out, const float* scale, float noise_scale,
-    unsigned long long seed, const unsigned long long* dp_step, const GatherArgs& ga) {
+    unsigned long long seed, const unsigned long long* dp_step, const GatherArgs& ga, const float* anchor = nullptr,
+    float mu = 0.f) {
   constexpr int NT = RED_COLS * RED_ROWG;
   const int apply = COHORT ? 1 : flags & kRedApply, nesterov = flags & kRedNesterov;
   if ((int)blockIdx.x >= nred) {  // block-uniform: gather blocks never reach the barrier below
@@ -1276,6 +1282,8 @@ __device__ __forceinline__ void slab_reduce_body(
   const bool upd = rg == 0 && col < P && apply;
   const float p0 = upd ? params[col] : 0.f;
   const float m0 = (upd && momentum != 0.f) ? mom[col] : 0.f;
+  float a0 = 0.f;
+  if constexpr (PROX) a0 = upd ? anchor[col] : 0.f;
   float noise = 0.f;  // drawn before the slab reads, under their latency
   if constexpr (DP)
     if (rg == 0 && col < P && noise_scale != 0.f) noise = noise_scale * dp_normal(col, seed, dp_step[0] - 1ull);
@@ -1313,6 +1321,7 @@ __device__ __forceinline__ void slab_reduce_body(
       if (apply) {
         const float p = p0;
         float d = gsum + wd * p;
+        if constexpr (PROX) d += mu * (p - a0);
         if (momentum != 0.f) {
           const float bm = momentum * m0 + d;
           mom[col] = bm;
@@ -1718,9 +1727,22 @@ RedGeom red_geom(int P, int M, const GatherArgs* gather, bool cohort = false) {
   return g;
 }
 
+// FedProx (``anchor``, ``mu``; slab_reduce_body's PROX form).  The launches are defined at the end of the file, where
+// the two prox kernels are first named: they are then instantiated behind every older kernel.
+int check_prox(const float* anchor, float mu) { return (!anchor || mu < 0.f) ? ecg::kBadArg : ecg::kOk; }
+int prox_reduce_launch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
+                       float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
+                       unsigned char* wprep, const float* anchor, float mu, hipStream_t stream,
+                       const GatherArgs* gather);
+
+// ``mu`` != 0: the prox kernel on ``anchor``; mu == 0 (the default): the launch it always was.
 int reduce_dispatch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
                     float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
-                    unsigned char* wprep, hipStream_t stream, const GatherArgs* gather = nullptr) {
+                    unsigned char* wprep, hipStream_t stream, const GatherArgs* gather = nullptr,
+                    const float* anchor = nullptr, float mu = 0.f) {
+  if (mu != 0.f)
+    return prox_reduce_launch(slab, G, stride, P, params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply,
+                              wprep, anchor, mu, stream, gather);
   const int st = check_reduce(G, stride, P, apply, params, momentum, mom);
   if (st) return st;
   const RedGeom g = red_geom(P, 1, gather);
@@ -1900,6 +1922,13 @@ struct EcgTinyRound {
   // Without xpk, ``prepack`` is kPrepackNone.  Every form computes the same bits.
   const void* xpk;
   int prepack;
+  // FedProx (prox_mu > 0; not with DP-SGD): every step's gradient gains prox_mu * (w - prox_anchor), prox_anchor [P]
+  // a buffer of its own (never ``params``).  With prox_snapshot the round's first launch copies params -> prox_anchor
+  // (prox_snapshot_kernel, enqueued and captured alike: a replayed graph re-anchors every round); without it the
+  // anchor is read as the caller left it.  prox_mu == 0: the other two are not read, today's launches.
+  float prox_mu;
+  float* prox_anchor;
+  int prox_snapshot;
 };
 enum { kPrepackNone = 0, kPrepackGather = 1, kPrepackDirect = 2 };
 
@@ -1922,6 +1951,8 @@ static int check_round(const EcgTinyRound* r) {
   }
   if (r->dp_clip < 0.f || r->dp_sigma < 0.f || (r->dp_sigma > 0.f && r->dp_clip == 0.f)) return ecg::kBadArg;
   if (r->dp_clip > 0.f && (!r->dp_scale || !r->dp_step)) return ecg::kBadArg;
+  if (r->prox_mu < 0.f) return ecg::kBadArg;
+  if (r->prox_mu > 0.f && (!r->prox_anchor || r->prox_anchor == r->params || r->dp_clip > 0.f)) return ecg::kBadArg;
   return check_step_args(r->L, r->nc, r->B, r->slab_stride, 0, r->prec == 1);
 }
 
@@ -1964,11 +1995,18 @@ static void gather_read(StepArgs& a, const GatherArgs& ga, const GatherBufs& g, 
   }
 }
 
-// Enqueue a checked round on ``stream`` (a capturing stream included): two launches per step, three with DP-SGD.
+// Enqueue a checked round on ``stream`` (a capturing stream included): two launches per step, three with DP-SGD;
+// FedProx with a snapshot adds one launch per round in front.
 // (Warm-up loads of the next step's windows in the step kernel's tail measured neutral - 11.11 vs 11.08 us/step,
 // the windows already sit in the Infinity Cache; profiles/r2/bench_prefetch.txt - and were removed.)
+static int prox_snapshot_launch(const float* params, float* anchor, int P, hipStream_t stream);  // (end of the file)
+
 static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
   const int P = make_layout(r.nc).P;
+  if (r.prox_mu > 0.f && r.prox_snapshot) {
+    const int st = prox_snapshot_launch(r.params, r.prox_anchor, P, stream);
+    if (st) return st;
+  }
   unsigned char* wprep = static_cast<unsigned char*>(r.wprep);
   const __bf16* xpk = static_cast<const __bf16*>(r.xpk);
   const bool gathers = r.xg || r.prepack == kPrepackGather;
@@ -1993,7 +2031,7 @@ static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
                               stream, gather_next ? &ga : nullptr);
     else
       st = reduce_dispatch(r.slab, r.B, r.slab_stride, P, r.params, r.mom, nullptr, r.loss_acc, r.lr, r.momentum, r.wd,
-                           r.nesterov, 1, wprep, stream, gather_next ? &ga : nullptr);
+                           r.nesterov, 1, wprep, stream, gather_next ? &ga : nullptr, r.prox_anchor, r.prox_mu);
     if (st) return st;
   }
   return ecg::kOk;
@@ -2157,6 +2195,10 @@ struct EcgTinyCohortRound {
   // when the round ends, and server_opt, server_m and server_v are not read; it needs cdp_scale, cdp_norm and
   // cdp_round.  Null: the round issues the launches it issues without this field.
   float* server_delta;
+  // FedProx (prox_mu > 0): every client's local steps add prox_mu * (w - global_params) to the gradient.  The anchor is
+  // ``global_params`` itself - the fan-out leaves the round's starting weights there and nothing writes them before
+  // the close, whichever close it is, nor with fanout == 0.  prox_mu == 0: the launches of before.
+  float prox_mu;
 };
 
 ECG_API int ecg_tiny_cohort_round_sizeof(void) { return (int)sizeof(EcgTinyCohortRound); }
@@ -2179,9 +2221,16 @@ int cohort_step_dispatch(int prec, const StepArgs& a, int M, hipStream_t stream)
 }
 
 // The cohort reduce + SGD of one step: M x the plain reduce's blocks, then the gather blocks of the next step.
+int cohort_prox_reduce_launch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
+                              float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
+                              const float* anchor, float mu, hipStream_t stream, const GatherArgs* gather);  // (end)
 int cohort_reduce_dispatch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
                            float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
-                           hipStream_t stream, const GatherArgs* gather = nullptr) {
+                           hipStream_t stream, const GatherArgs* gather = nullptr, const float* anchor = nullptr,
+                           float mu = 0.f) {
+  if (mu != 0.f)  // FedProx: the prox kernel, one anchor for all M clients; mu == 0: the launch it always was
+    return cohort_prox_reduce_launch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov, wprep,
+                                     anchor, mu, stream, gather);
   const int st = check_reduce(G, stride, P, 1, params, momentum, mom);
   if (st) return st;
   const RedGeom g = red_geom(P, M, gather, true);
@@ -2230,6 +2279,7 @@ static int check_cohort_round(const EcgTinyCohortRound* r) {
   const long rows = (long)r->M * r->B;
   if (rows * r->slab_stride * 4 > INT_MAX || rows * (pack_ldb(r->L) + 8) * 4 > INT_MAX) return ecg::kTooLarge;
   if (r->cdp_clip < 0.f || r->cdp_sigma < 0.f || r->server_lr < 0.f) return ecg::kBadArg;
+  if (r->prox_mu < 0.f) return ecg::kBadArg;
   if (r->cdp_sigma > 0.f && r->cdp_clip == 0.f) return ecg::kBadArg;
   if (cohort_dp_on(*r) && (!r->cdp_scale || !r->cdp_norm || !r->cdp_round)) return ecg::kBadArg;
   if (r->server_delta) return (!r->cdp_scale || !r->cdp_norm || !r->cdp_round) ? ecg::kBadArg : ecg::kOk;
@@ -2261,7 +2311,7 @@ static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream)
     int st = cohort_step_dispatch(r.prec, a, r.M, stream);
     if (st) return st;
     st = cohort_reduce_dispatch(r.slab, r.B, r.M, r.slab_stride, P, r.params, r.mom, r.loss_acc, r.lr, r.momentum, r.wd,
-                                r.nesterov, wprep, stream, gather_next ? &ga : nullptr);
+                                r.nesterov, wprep, stream, gather_next ? &ga : nullptr, r.global_params, r.prox_mu);
     if (st) return st;
   }
   if (r.server_delta)
@@ -2576,4 +2626,99 @@ ECG_API int ecg_server_opt_step(float* g, const float* delta, long n, int opt, f
 #undef ECG_SERVER_STEP_LAUNCH
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
+}
+
+// ---------------------------------------------------------------------------- FedProx (proximal local steps)
+// slab_reduce_body's PROX form in the plain and the cohort kernel, and the snapshot a single client's round starts
+// with.  The step kernel is not involved: the proximal term only enters the SGD epilogue, as one more load per updating
+// thread (under the slab reads) and a subtract and a multiply-add.  (Defined and first named here, behind every older
+// kernel.)
+namespace {
+
+// The plain kernel's argument order with ``anchor``, ``mu`` in front of ``ga``.
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_prox_sgd_kernel(
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
+    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, float* __restrict__ grad_out,
+    const float* __restrict__ anchor, float mu, GatherArgs ga) {
+  slab_reduce_body<RED_COLS, false, false, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
+                                                 loss_acc, grad_out, nullptr, 0.f, 0ull, nullptr, ga, anchor, mu);
+}
+
+// The cohort kernel's argument order with ``anchor`` [P] - one vector for all M clients - and ``mu`` in front of ``ga``.
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_prox_sgd_kernel(
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
+    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, const float* __restrict__ anchor, float mu,
+    GatherArgs ga) {
+  slab_reduce_body<RED_COLS, false, true, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
+                                                loss_acc, nullptr, nullptr, 0.f, 0ull, nullptr, ga, anchor, mu);
+}
+
+// anchor[0:P] = params[0:P]: the first launch of a single client's FedProx round.
+template <int NT>
+__global__ __launch_bounds__(NT) void prox_snapshot_kernel(const float* __restrict__ params, float* __restrict__ anchor,
+                                                           int P) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i < P) anchor[i] = params[i];
+}
+
+int prox_reduce_launch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
+                       float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
+                       unsigned char* wprep, const float* anchor, float mu, hipStream_t stream,
+                       const GatherArgs* gather) {
+  int st = check_reduce(G, stride, P, apply, params, momentum, mom);
+  if (!st) st = check_prox(anchor, mu);
+  if (st) return st;
+  const RedGeom g = red_geom(P, 1, gather);
+  hipLaunchKernelGGL(slab_reduce_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
+                     params, mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc,
+                     grad_out, anchor, mu, g.ga);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+int cohort_prox_reduce_launch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
+                              float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
+                              const float* anchor, float mu, hipStream_t stream, const GatherArgs* gather) {
+  int st = check_reduce(G, stride, P, 1, params, momentum, mom);
+  if (!st) st = check_prox(anchor, mu);
+  if (st) return st;
+  const RedGeom g = red_geom(P, M, gather, true);
+  hipLaunchKernelGGL(slab_reduce_cohort_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream,
+                     slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
+                     anchor, mu, g.ga);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+}  // namespace
+
+static int prox_snapshot_launch(const float* params, float* anchor, int P, hipStream_t stream) {
+  hipLaunchKernelGGL(prox_snapshot_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, params, anchor, P);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+// ecg_slab_reduce_sgd with the proximal term mu * (p - anchor[col]) in the gradient (``anchor`` [P], mu >= 0).  It
+// always launches the prox kernel: mu == 0 gives ecg_slab_reduce_sgd's bits.
+ECG_API int ecg_slab_reduce_prox_sgd(const float* slab, int G, int stride, int P, float* params, float* mom,
+                                     float* grad_out, float* loss_acc, float lr, float momentum, float wd, int nesterov,
+                                     int apply, void* wprep, const float* anchor, float mu, hipStream_t stream) {
+  if (wprep && !apply) return ecg::kBadArg;
+  return prox_reduce_launch(slab, G, stride, P, params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply,
+                            static_cast<unsigned char*>(wprep), anchor, mu, stream, nullptr);
+}
+
+// The cohort twin on caller-supplied buffers: M clients' G slab rows each, weights / momenta at the cohort parameter
+// stride, images at the cohort image stride (nullable), loss words loss_acc[M] (nullable), one ``anchor`` [P] for all.
+ECG_API int ecg_slab_reduce_cohort_prox_sgd(const float* slab, int G, int M, int stride, int P, float* params,
+                                            float* mom, float* loss_acc, float lr, float momentum, float wd,
+                                            int nesterov, void* wprep, const float* anchor, float mu,
+                                            hipStream_t stream) {
+  if (!slab || M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
+  return cohort_prox_reduce_launch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov,
+                                   static_cast<unsigned char*>(wprep), anchor, mu, stream, nullptr);
 }

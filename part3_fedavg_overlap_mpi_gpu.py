@@ -25,6 +25,11 @@ FedYogi; state kept in the per-rank checkpoint; the three adaptive ones under --
 with --server-scope global)
 --server-scope {rank,global} (global, needs --clients-per-gpu: the ranks' cohort deltas are all-reduced in place of
 their weights and every rank takes one replicated server step on the average - a global server optimizer)
+--prox-mu mu (FedProx: every local step's gradient gains mu * (w - the weights the round started from); TinyECG on the
+fused backend, with or without --clients-per-gpu, any model on the torch backend; not with --dp-clip, --sync ddp, fp16
+AMP or --overlap delayed)
+--client-partition {contiguous,shards} --client-shards s (needs --clients-per-gpu: "shards" deals every virtual client s
+runs of the GPU's label-sorted training windows - label-skewed, non-IID clients - instead of a contiguous slice)
 """
 from __future__ import annotations
 
