@@ -1,4 +1,5 @@
-"""Cohorts of virtual FedAvg clients on one GPU (Python side of the cohort entries of csrc/kernels/tiny_ecg_step.hip).
+"""Cohorts of virtual FedAvg clients on one GPU (Python side of the cohort entries of csrc/kernels/tiny_ecg_step.hip
+and, for the close of a round, csrc/kernels/tiny_ecg_close.hip).
 
 The fused step kernel runs one workgroup per window, so a client with a small batch leaves most of the GPU idle.
 ``FusedCohortTrainer`` holds ``clients`` virtual clients (contiguous partitions of its windows) and trains a

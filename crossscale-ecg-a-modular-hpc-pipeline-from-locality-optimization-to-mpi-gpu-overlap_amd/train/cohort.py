@@ -15,7 +15,7 @@ with g the global weights the round started from, ``d_c = p_c - g`` over all P p
 in fp32, ``nu = fp32(sigma * C / (M * sqrt(W)))`` with sigma = ``client_dp_noise`` and W = ``world_size`` (the driver
 averages W ranks' weights, which leaves noise of standard deviation sigma * C / (M * W) on a mean of sensitivity
 C / (M * W)), and ``z = philox.normal(client_dp_seed, round, P, stream=1)``: the definition that
-``cohort_dp_mean_kernel`` of csrc/kernels/tiny_ecg_step.hip implements.
+``cohort_dp_mean_kernel`` of csrc/kernels/tiny_ecg_close.hip implements.
 
 A server optimizer (``server_opt`` sgdm / adagrad / adam / yogi; ``train/server_opt.py`` states the rules) takes the
 bracket above - Delta, the averaged, clipped, noised delta - as its pseudo-gradient in place of the plain step

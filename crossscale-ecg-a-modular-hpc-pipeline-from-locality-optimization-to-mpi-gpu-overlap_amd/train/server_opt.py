@@ -11,7 +11,7 @@ paper's ``v_{-1} >= tau^2``), no bias correction, everything in fp32:
 * adagrad, adam, yogi: ``g += eta m / (sqrt(v) + tau)`` with the new ``m`` and ``v``
 
 ``eta`` is the server step size ``server_lr``.  This is the definition that ``cohort_server_opt_kernel`` and, from
-Delta on, ``server_step_kernel`` of csrc/kernels/tiny_ecg_step.hip implement; ``server_opt_step`` is its torch form
+Delta on, ``server_step_kernel`` of csrc/kernels/tiny_ecg_close.hip implement; ``server_opt_step`` is its torch form
 (the eager reference and the CPU path).  ``SERVER_SCOPES`` names where the step is taken: per rank on the rank's own
 Delta, or once ("global") on the all-reduced mean of the ranks' Deltas.
 """

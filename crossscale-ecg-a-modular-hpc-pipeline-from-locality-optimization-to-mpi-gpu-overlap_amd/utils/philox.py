@@ -2,7 +2,8 @@
 
 Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11), written from the
 paper and checked against the Random123 known-answer vectors (tests/test_philox_cpu.py).  Conventions, the same as
-``dp_normal`` in csrc/kernels/tiny_ecg_step.hip:
+``dp_normal`` in csrc/kernels/tiny_ecg_step.hip and ``cohort_dp_normal`` in csrc/kernels/tiny_ecg_close.hip (the rounds
+themselves: ``philox4x32_10`` in csrc/include/tiny_ecg.h):
 
 * counter ``(i, t & 0xffffffff, t >> 32, stream)``, key ``(seed & 0xffffffff, seed >> 32)``: ``i`` the flat parameter
   index, ``t`` the 64-bit DP step counter, ``seed`` the 64-bit DP seed; ``stream`` is 0 for DP-SGD (``dp_normal``) and

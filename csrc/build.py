@@ -51,8 +51,12 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-f
 # loads without a scalar-load round trip; their parameter order is chosen for it (comment at tiny_ecg_step_kernel).
 # The compiler keeps a prologue that loads the same dwords, so the code object also runs where the firmware does not
 # preload.  Measurements: profiles/r10/tiny_kernarg_preload.txt.
-FILE_FLAGS = {"tiny_ecg_step.hip": ["-fno-honor-nans", "-fno-signed-zeros",
-                                    "-mllvm", "-amdgpu-kernarg-preload-count=16"]}
+#
+# tiny_ecg_close.hip (the close of a cohort round) was part of tiny_ecg_step.hip and keeps its flags - one list, named
+# twice: -fno-honor-nans -fno-signed-zeros and the kernarg preload are part of those kernels' recorded bits (the split
+# close equals the fused close bitwise, sgdm with beta1 = 0 equals the DP close) and float64 bounds.
+TINY_FLAGS = ["-fno-honor-nans", "-fno-signed-zeros", "-mllvm", "-amdgpu-kernarg-preload-count=16"]
+FILE_FLAGS = {"tiny_ecg_step.hip": TINY_FLAGS, "tiny_ecg_close.hip": TINY_FLAGS}
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-pthread"]
 
 

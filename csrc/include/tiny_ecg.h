@@ -1,6 +1,6 @@
-// TinyECG declarations shared by the training step (kernels/tiny_ecg_step.hip) and the evaluation kernel
-// (kernels/tiny_ecg_eval.hip): the flat parameter layout, the prepared-fragment image and the small device helpers
-// both files use.
+// TinyECG declarations shared by the training step (kernels/tiny_ecg_step.hip), the close of a cohort round
+// (kernels/tiny_ecg_close.hip) and the evaluation kernel (kernels/tiny_ecg_eval.hip): the flat parameter layout, the
+// prepared-fragment image, the cohort stride, the Philox rounds and the small device helpers they use.
 #pragma once
 #include "ecg_common.h"
 
@@ -77,6 +77,25 @@ __device__ __forceinline__ float row16_sum(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xf, 0xf, true));
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, true));
   return v;
+}
+
+// Floats between two clients' weights (and momenta) in a cohort's ``params`` / ``mom``: >= P, a multiple of 64.
+__host__ __device__ constexpr int cohort_pstride(int P) { return (P + 63) / 64 * 64; }
+
+// Philox4x32-10 (Salmon et al., SC'11): the counter-based generator behind both DP noise streams (dp_normal in
+// kernels/tiny_ecg_step.hip, cohort_dp_normal in kernels/tiny_ecg_close.hip; utils/philox.py is the host twin).
+__host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    c[1] = (uint32_t)p1;
+    c[3] = (uint32_t)p0;
+    c[0] = n0;
+    c[2] = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
 }
 
 }  // namespace tiny

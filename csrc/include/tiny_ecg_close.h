@@ -1,0 +1,38 @@
+// The close of a cohort round with a server step, as kernels/tiny_ecg_step.hip's round calls it and
+// kernels/tiny_ecg_close.hip defines it.
+#pragma once
+#include "ecg_common.h"
+
+namespace ecg {
+namespace tiny {
+
+// One close: M clients' weights ``params`` at the cohort stride, the round's starting weights ``global`` [P], the clip
+// norm (0: none), the noise multiplier of this rank's share, the server step size (0 means 1), the Philox key and the
+// device round word, the [M] clip factors and delta norms it reports, and the server optimizer (0 none, 1 sgdm, 2
+// adagrad, 3 adam, 4 yogi) with its state m / v [P].  ``delta`` (nullable) [P]: the split close - the averaged, clipped,
+// noised delta goes there, ``global`` is only read, and opt, m and v are not read at all.
+struct CohortClose {
+  const float* params;
+  float* global;
+  int P, M;
+  float clip, sigma, server_lr;
+  unsigned long long seed;
+  unsigned long long* round_word;
+  float* scale;
+  float* norm;
+  int opt;
+  float beta1, beta2, tau;
+  float* m;
+  float* v;
+  float* delta;
+};
+
+// kOk, or kBadArg for a close that cohort_close must not be given.
+int check_cohort_close(const CohortClose& c);
+
+// The two launches of a checked close: cohort_delta_scale_kernel, then cohort_delta_kernel (``delta`` set),
+// cohort_server_opt_kernel<opt> (opt != 0) or cohort_dp_mean_kernel.
+int cohort_close(const CohortClose& c, hipStream_t stream);
+
+}  // namespace tiny
+}  // namespace ecg

@@ -28,8 +28,8 @@
 // Precision: bf16 MFMA operands, fp32 accumulation, fp32 master weights/optimizer state (native bf16 AMP).
 #include "../include/ecg_common.h"
 #include "../include/tiny_ecg.h"
+#include "../include/tiny_ecg_close.h"
 
-#include <cfloat>
 #include <climits>
 #include <cstdint>
 #include <cstdlib>
@@ -988,7 +988,6 @@ struct TinySample {
 //         to back) with client c's weights and image, which lie at the fixed strides cohort_pstride /
 //         kCohortWprepStride from ``params`` / ``wprep``.  Both strides follow from ``nc``, so the argument list is
 //         unchanged, and c is a workgroup id, not a division.  ``inv_B`` is 1 / B of one client.
-__host__ __device__ constexpr int cohort_pstride(int P) { return (P + 63) / 64 * 64; }  // floats between clients
 constexpr int kCohortWprepStride = (WP_BYTES + 127) / 128 * 128;                          // bytes between images
 
 template <int WAVES, int MODE, bool F32, bool PF, bool PK = false>
@@ -1236,22 +1235,29 @@ __device__ __forceinline__ void gather_block(const GatherArgs& ga, int nred) {
 }
 static_assert(kPackLead == 4, "gather_block's 4-float form writes the lead as one 8-byte unit");
 
-// defined with the DP kernels
-__device__ inline float dp_normal(int i, unsigned long long seed, unsigned long long t);
+// DP-SGD noise is counter-based so that a graph replay, an enqueued round and the torch backend (utils/philox.py) draw
+// the same z: philox4x32_10 with counter (i, t lo, t hi, 0) and key (seed lo, seed hi), i the parameter index and t the
+// 64-bit DP step counter; u1 = ((w0 >> 8) + 1) * 2^-24 in (0, 1], u2 = (w1 >> 8) * 2^-24 in [0, 1),
+// z = sqrt(-2 ln u1) * cos(2 pi u2) with the accurate logf / sqrtf / cosf (|z| <= 5.77).
+__device__ inline float dp_normal(int i, unsigned long long seed, unsigned long long t) {
+  uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)(t >> 32), 0u};
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const float u1 = (float)((c[0] >> 8) + 1u) * 0x1p-24f, u2 = (float)(c[1] >> 8) * 0x1p-24f;
+  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+}
 
-// The one body of the three reduce kernels.  DP: every loaded gradient value is multiplied by its row's clip factor
+// The one body of the reduce kernels.  DP: every loaded gradient value is multiplied by its row's clip factor
 // ``scale[row]`` and ``noise_scale`` * z_col is added to the column sum before the epilogue (the loss column is neither
 // scaled nor noised; noise_scale == 0: no noise is drawn).  COHORT: block c * nblk + j (nblk = the single-client block
 // count) is block j on client c's G slab rows, weights, momentum, image and loss word; the update is always applied.
-// Column-to-block map, row chunking, summation order and epilogue are these lines for all three, so DP with every
-// scale[b] == 1 and no noise, and a cohort of one, give the plain kernel's bits.  The pointers carry no __restrict__
+// Column-to-block map, row chunking, summation order and epilogue are these lines for every form, so DP with every
+// scale[b] == 1 and no noise, a cohort of one, and PROX with mu == 0 give the plain kernel's bits.  The pointers carry no __restrict__
 // here: the kernels' own parameters do, and a second set of alias scopes from the inlined body changes the gather
 // branch's code (profiles/r12/tiny_reduce_merge.txt).
 // PROX (FedProx, Li et al. 2020): the gradient that enters the epilogue gains mu * (p - anchor[col]), the gradient of
 // mu/2 * |w - anchor|^2: d = gsum + wd * p + mu * (p - a), which then passes through momentum and nesterov like any
 // other gradient (torch.optim.SGD with mu * (p - a) added to p.grad).  ``anchor`` [P] is shared by all clients of a cohort
-// (never offset by the client stride); the updating thread loads it beside p0 / m0, before the slab reads.  The two
-// arguments are trailing defaults: the three older kernels' calls, and their code, stay as they were.
+// (never offset by the client stride); the updating thread loads it beside p0 / m0, before the slab reads.
 template <int RED_COLS, bool DP, bool COHORT, bool PROX = false>
 __device__ __forceinline__ void slab_reduce_body(
     const float* slab, float* params, float* mom, int nred, int G, int stride, int P, int flags, float momentum,
@@ -1351,36 +1357,10 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_sgd_kernel(
 // ---------------------------------------------------------------------------- DP-SGD (per-sample clip + noise)
 // The slab already holds one gradient row per sample, so DP-SGD only changes the reduce side: a row-norm launch
 // writes the clip factors c_b = min(1, C / n_b) and ``slab_reduce_dp_sgd_kernel`` sums c_b * row_b, adds
-// sigma * C / B * z_i and runs the same SGD / wprep / gather epilogue.  The step kernel is not involved.
-//
-// Noise is counter-based so that a graph replay, an enqueued round and the torch backend (utils/philox.py) draw the
-// same z: Philox4x32-10 (Salmon et al., SC'11) with counter (i, t lo, t hi, 0) and key (seed lo, seed hi), i the
-// parameter index and t the 64-bit DP step counter; u1 = ((w0 >> 8) + 1) * 2^-24 in (0, 1], u2 = (w1 >> 8) * 2^-24
-// in [0, 1), z = sqrt(-2 ln u1) * cos(2 pi u2) with the accurate logf / sqrtf / cosf (|z| <= 5.77).
-__host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
-__device__ inline float dp_normal(int i, unsigned long long seed, unsigned long long t) {
-  uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)(t >> 32), 0u};
-  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const float u1 = (float)((c[0] >> 8) + 1u) * 0x1p-24f, u2 = (float)(c[1] >> 8) * 0x1p-24f;
-  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
-}
+// sigma * C / B * z_i (dp_normal, above the body) and runs the same SGD / wprep / gather epilogue.  The step kernel is
+// not involved.
 
 // Diagnostic: z[i] for i < P of step t (the values the DP reduce adds, without the sigma * C / B factor).
-// (The DP kernels are templates so that hipcc emits them after every older kernel of this file: the older kernels'
-// assembly, label numbers included, stays what scripts/diff_device_asm.py saw before DP-SGD existed.)
 template <int NT>
 __global__ __launch_bounds__(NT) void dp_noise_kernel(float* __restrict__ z, int P, unsigned long long seed,
                                                       unsigned long long t) {
@@ -1443,8 +1423,7 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_dp_sgd_kernel
 // workgroups and one reduce launch of M x the plain reduce's blocks per step, between a fan-out of the global weights
 // and the mean of the clients' weights.  Client c's weights / momentum are at ``params`` / ``mom`` + c * pstride
 // floats (cohort_pstride), its image at ``wprep`` + c * kCohortWprepStride bytes, its loss word at loss_acc[c] and its
-// slab rows at [c * B, (c + 1) * B).  The step kernel is tiny_ecg_step_kernel's MODE 3.  (Templates, like the DP
-// kernels: emitted after every older kernel.)
+// slab rows at [c * B, (c + 1) * B).  The step kernel is tiny_ecg_step_kernel's MODE 3.
 // slab_reduce_body's COHORT form, M clients in one launch: blocks >= nred = M * nblk gather the next step's M * G rows
 // (ga.B).  The plain kernel's argument order without ``grad_out``; the apply flag is not read.
 template <int RED_COLS>
@@ -1456,102 +1435,41 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_sgd_ke
                                           loss_acc, nullptr, nullptr, 0.f, 0ull, nullptr, ga);
 }
 
-// Start of a cohort round: every client's weights = the global weights, every momentum = 0 (virtual clients keep no
-// state between rounds).  grid (ceil(P / NT), M); the pstride - P padding floats of a client are not written.
+// ---------------------------------------------------------------------------- FedProx (proximal local steps)
+// slab_reduce_body's PROX form in the plain and the cohort kernel, and the snapshot a single client's round starts
+// with.  The step kernel is not involved: the proximal term only enters the SGD epilogue, as one more load per updating
+// thread (under the slab reads) and a subtract and a multiply-add.
+// The plain kernel's argument order with ``anchor``, ``mu`` in front of ``ga``.
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_prox_sgd_kernel(
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
+    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, float* __restrict__ grad_out,
+    const float* __restrict__ anchor, float mu, GatherArgs ga) {
+  slab_reduce_body<RED_COLS, false, false, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
+                                                 loss_acc, grad_out, nullptr, 0.f, 0ull, nullptr, ga, anchor, mu);
+}
+
+// The cohort kernel's argument order with ``anchor`` [P] - one vector for all M clients - and ``mu`` in front of ``ga``.
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_prox_sgd_kernel(
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
+    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, const float* __restrict__ anchor, float mu,
+    GatherArgs ga) {
+  slab_reduce_body<RED_COLS, false, true, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
+                                                loss_acc, nullptr, nullptr, 0.f, 0ull, nullptr, ga, anchor, mu);
+}
+
+// anchor[0:P] = params[0:P]: the first launch of a single client's FedProx round.
 template <int NT>
-__global__ __launch_bounds__(NT) void cohort_fanout_kernel(const float* __restrict__ global_params,
-                                                           float* __restrict__ params, float* __restrict__ mom, int P) {
+__global__ __launch_bounds__(NT) void prox_snapshot_kernel(const float* __restrict__ params, float* __restrict__ anchor,
+                                                           int P) {
   const int i = blockIdx.x * NT + threadIdx.x;
-  if (i >= P) return;
-  const long o = (long)blockIdx.y * cohort_pstride(P) + i;
-  params[o] = global_params[i];
-  if (mom) mom[o] = 0.f;
+  if (i < P) anchor[i] = params[i];
 }
 
-// End of a cohort round: global[i] = (((p_0[i] + p_1[i]) + ...) + p_{M-1}[i]) * inv_M in fp32, clients in ascending
-// order (inv_M = 1.0f / M, rounded once on the host): one fixed order, so the mean is reproducible.
-template <int NT>
-__global__ __launch_bounds__(NT) void cohort_mean_kernel(const float* __restrict__ params,
-                                                         float* __restrict__ global_params, int P, int M, float inv_M) {
-  const int i = blockIdx.x * NT + threadIdx.x;
-  if (i >= P) return;
-  const int pstride = cohort_pstride(P);
-  float s = params[i];
-  for (int c = 1; c < M; ++c) s += params[(long)c * pstride + i];
-  global_params[i] = s * inv_M;
-}
-
-// ---------------------------------------------------------------------------- client-level DP (DP-FedAvg close)
-// The close of a cohort round with client-level differential privacy, in place of cohort_mean_kernel: with g the
-// round's starting weights (what the fan-out read: ``global_params`` is untouched until here), d_c = p_c - g,
-// n_c = |d_c|_2 and s_c = min(1, C / n_c) (n_c == 0 -> 1),
-//   g_new[i] = g[i] + eta * ((((s_0 d_0[i] + s_1 d_1[i]) + ...) + s_{M-1} d_{M-1}[i]) * inv_M + nu * z_i),
-// clients in ascending order in fp32, nu = sigma * C / M rounded once on the host (nu == 0: nothing is drawn).
-// (Templates, like the DP and cohort kernels: emitted after every older kernel.)
-//
-// z_i: dp_normal's generator on its own stream - the last counter word is 1 where dp_normal has 0, so the counters
-// of the two noise streams never coincide, whatever the seeds and step / round numbers.  r is the 64-bit round counter.
-__device__ inline float cohort_dp_normal(int i, unsigned long long seed, unsigned long long r) {
-  uint32_t c[4] = {(uint32_t)i, (uint32_t)r, (uint32_t)(r >> 32), 1u};
-  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const float u1 = (float)((c[0] >> 8) + 1u) * 0x1p-24f, u2 = (float)(c[1] >> 8) * 0x1p-24f;
-  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
-}
-
-// Diagnostic: z[i] for i < P of round r (the values cohort_dp_mean_kernel adds, without the nu factor).
-template <int NT>
-__global__ __launch_bounds__(NT) void cohort_dp_noise_kernel(float* __restrict__ z, int P, unsigned long long seed,
-                                                             unsigned long long r) {
-  const int i = blockIdx.x * NT + threadIdx.x;
-  if (i < P) z[i] = cohort_dp_normal(i, seed, r);
-}
-
-// Clip factors of a cohort: one wave per client, scale[c] = s_c and norm[c] = n_c (reported, not read by the close).
-// Fixed summation order (per lane in column order, then a butterfly over the wave), no atomics.  Exactly P floats of a
-// client are read: the pstride - P padding floats are never written.  Thread 0 of block 0 advances the round counter
-// (dp_row_scale_kernel's pattern: its only writer; its only reader is the close launched next, which therefore draws
-// round ``round_word[0] - 1``), so a replayed graph draws fresh noise.
-constexpr int CDP_CLIENTS_PER_BLOCK = 4;
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void cohort_delta_scale_kernel(
-    const float* __restrict__ params, const float* __restrict__ global_params, int P, int M, float clip,
-    float* __restrict__ scale, float* __restrict__ norm, unsigned long long* __restrict__ round_word) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) round_word[0] = round_word[0] + 1ull;
-  const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * WAVES + (threadIdx.x >> 6);
-  if (c >= M) return;  // wave-uniform
-  const float* p = params + (long)c * cohort_pstride(P);
-  float ss = 0.f;
-  for (int i = lane; i < P; i += 64) {
-    const float d = p[i] - global_params[i];
-    ss += d * d;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-  if (lane == 0) {
-    const float n = sqrtf(ss);
-    norm[c] = n;
-    scale[c] = n > 0.f ? fminf(1.f, clip / n) : 1.f;
-  }
-}
-
-// The close itself, one thread per parameter.  The noise is drawn before the client loads, under their latency.
-template <int NT>
-__global__ __launch_bounds__(NT) void cohort_dp_mean_kernel(
-    const float* __restrict__ params, float* __restrict__ global_params, int P, int M, float inv_M,
-    const float* __restrict__ scale, float server_lr, float noise_scale, unsigned long long seed,
-    const unsigned long long* __restrict__ round_word) {
-  const int i = blockIdx.x * NT + threadIdx.x;
-  if (i >= P) return;
-  const int pstride = cohort_pstride(P);
-  float noise = 0.f;
-  if (noise_scale != 0.f) noise = noise_scale * cohort_dp_normal(i, seed, round_word[0] - 1ull);
-  const float g = global_params[i];
-  float s = scale[0] * (params[i] - g);
-  for (int c = 1; c < M; ++c) s += scale[c] * (params[(long)c * pstride + i] - g);
-  global_params[i] = g + server_lr * (s * inv_M + noise);
-}
-
+// ---------------------------------------------------------------------------- the dataset packed once
 // The whole dataset as packed rows, once: out[n] = [kPackLead zeros][bf16(X[n][0 .. L-1])][zeros up to ldb] for every
 // row n < N - the layout and the cast (ecg::to_bf16) of gather_block's xbg rows, so a step that reads out[idx[b]]
 // sees the bits it would have seen in the gathered row.  One block per row (rows beyond the grid: grid stride); every
@@ -1590,6 +1508,34 @@ __global__ __launch_bounds__(128) void tiny_pack_rows_kernel(const float* __rest
   }
 }
 
+// ---------------------------------------------------------------------------- cohort fan-out and mean
+// Start of a cohort round: every client's weights = the global weights, every momentum = 0 (virtual clients keep no
+// state between rounds).  grid (ceil(P / NT), M); the pstride - P padding floats of a client are not written.
+template <int NT>
+__global__ __launch_bounds__(NT) void cohort_fanout_kernel(const float* __restrict__ global_params,
+                                                           float* __restrict__ params, float* __restrict__ mom, int P) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= P) return;
+  const long o = (long)blockIdx.y * cohort_pstride(P) + i;
+  params[o] = global_params[i];
+  if (mom) mom[o] = 0.f;
+}
+
+// End of a cohort round: global[i] = (((p_0[i] + p_1[i]) + ...) + p_{M-1}[i]) * inv_M in fp32, clients in ascending
+// order (inv_M = 1.0f / M, rounded once on the host): one fixed order, so the mean is reproducible.  Every other close
+// of a round is ecg::tiny::cohort_close (kernels/tiny_ecg_close.hip).
+template <int NT>
+__global__ __launch_bounds__(NT) void cohort_mean_kernel(const float* __restrict__ params,
+                                                         float* __restrict__ global_params, int P, int M, float inv_M) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= P) return;
+  const int pstride = cohort_pstride(P);
+  float s = params[i];
+  for (int c = 1; c < M; ++c) s += params[(long)c * pstride + i];
+  global_params[i] = s * inv_M;
+}
+
+// ---------------------------------------------------------------------------- host launchers
 unsigned long long* g_stamps = nullptr;  // diagnostic phase stamps (ecg_tiny_set_stamps)
 
 FusedOpt no_fuse() {
@@ -1727,28 +1673,35 @@ RedGeom red_geom(int P, int M, const GatherArgs* gather, bool cohort = false) {
   return g;
 }
 
-// FedProx (``anchor``, ``mu``; slab_reduce_body's PROX form).  The launches are defined at the end of the file, where
-// the two prox kernels are first named: they are then instantiated behind every older kernel.
+// FedProx (``anchor``, ``mu``; slab_reduce_body's PROX form).
 int check_prox(const float* anchor, float mu) { return (!anchor || mu < 0.f) ? ecg::kBadArg : ecg::kOk; }
-int prox_reduce_launch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
-                       float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
-                       unsigned char* wprep, const float* anchor, float mu, hipStream_t stream,
-                       const GatherArgs* gather);
 
-// ``mu`` != 0: the prox kernel on ``anchor``; mu == 0 (the default): the launch it always was.
+// ``mu`` != 0 (or ``prox``, the stand-alone prox entry points): the prox kernel on ``anchor``; otherwise the plain
+// kernel, and ``anchor`` is not looked at.
 int reduce_dispatch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
                     float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
                     unsigned char* wprep, hipStream_t stream, const GatherArgs* gather = nullptr,
-                    const float* anchor = nullptr, float mu = 0.f) {
-  if (mu != 0.f)
-    return prox_reduce_launch(slab, G, stride, P, params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply,
-                              wprep, anchor, mu, stream, gather);
-  const int st = check_reduce(G, stride, P, apply, params, momentum, mom);
+                    const float* anchor = nullptr, float mu = 0.f, bool prox = false) {
+  prox = prox || mu != 0.f;
+  int st = check_reduce(G, stride, P, apply, params, momentum, mom);
+  if (!st && prox) st = check_prox(anchor, mu);
   if (st) return st;
   const RedGeom g = red_geom(P, 1, gather);
-  hipLaunchKernelGGL(slab_reduce_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab, params,
-                     mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc, grad_out,
-                     g.ga);
+  if (prox)
+    hipLaunchKernelGGL(slab_reduce_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
+                       params, mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc,
+                       grad_out, anchor, mu, g.ga);
+  else
+    hipLaunchKernelGGL(slab_reduce_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
+                       params, mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc,
+                       grad_out, g.ga);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+// anchor[0:P] = params[0:P], the first launch of a single client's FedProx round with a snapshot.
+int prox_snapshot_launch(const float* params, float* anchor, int P, hipStream_t stream) {
+  hipLaunchKernelGGL(prox_snapshot_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, params, anchor, P);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -1781,6 +1734,42 @@ int dp_reduce_dispatch(const float* slab, int G, int stride, int P, float* param
   hipLaunchKernelGGL(slab_reduce_dp_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
                      params, mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc,
                      grad_out, dp.scale, noise_scale, dp.seed, dp.step, g.ga);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
+// The cohort forms of the three kernels a production round launches: fp32; bf16 building its operands in LDS (a
+// round's first step: ``a.wprep`` null); bf16 on packed rows and the images (``a.packed``).  Arguments are checked
+// by check_cohort_round.
+int cohort_step_dispatch(int prec, const StepArgs& a, int M, hipStream_t stream) {
+  const bool w8 = pick_waves(a.L, prec == 1) == 8;
+  if (prec == 1)
+    return w8 ? launch_step<8, 3, true, false>(a, stream, M) : launch_step<16, 3, true, false>(a, stream, M);
+  if (a.packed)
+    return w8 ? launch_step<8, 3, false, true, true>(a, stream, M) : launch_step<16, 3, false, true, true>(a, stream, M);
+  if (a.wprep) return ecg::kBadArg;  // the unpacked prepared-fragment kernel has no cohort form
+  return w8 ? launch_step<8, 3, false, false>(a, stream, M) : launch_step<16, 3, false, false>(a, stream, M);
+}
+
+// The cohort reduce + SGD of one step: M x the plain reduce's blocks, then the gather blocks of the next step.
+// FedProx as in reduce_dispatch, one anchor for all M clients.
+int cohort_reduce_dispatch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
+                           float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
+                           hipStream_t stream, const GatherArgs* gather = nullptr, const float* anchor = nullptr,
+                           float mu = 0.f, bool prox = false) {
+  prox = prox || mu != 0.f;
+  int st = check_reduce(G, stride, P, 1, params, momentum, mom);
+  if (!st && prox) st = check_prox(anchor, mu);
+  if (st) return st;
+  const RedGeom g = red_geom(P, M, gather, true);
+  if (prox)
+    hipLaunchKernelGGL(slab_reduce_cohort_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream,
+                       slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
+                       anchor, mu, g.ga);
+  else
+    hipLaunchKernelGGL(slab_reduce_cohort_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
+                       params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
+                       g.ga);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -1885,6 +1874,27 @@ ECG_API int ecg_dp_noise(float* z, int P, unsigned long long seed, unsigned long
   hipLaunchKernelGGL(dp_noise_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, z, P, seed, t);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
+}
+
+// ecg_slab_reduce_sgd with the proximal term mu * (p - anchor[col]) in the gradient (``anchor`` [P], mu >= 0).  It
+// always launches the prox kernel: mu == 0 gives ecg_slab_reduce_sgd's bits.
+ECG_API int ecg_slab_reduce_prox_sgd(const float* slab, int G, int stride, int P, float* params, float* mom,
+                                     float* grad_out, float* loss_acc, float lr, float momentum, float wd, int nesterov,
+                                     int apply, void* wprep, const float* anchor, float mu, hipStream_t stream) {
+  if (wprep && !apply) return ecg::kBadArg;
+  return reduce_dispatch(slab, G, stride, P, params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply,
+                         static_cast<unsigned char*>(wprep), stream, nullptr, anchor, mu, true);
+}
+
+// The cohort twin on caller-supplied buffers: M clients' G slab rows each, weights / momenta at the cohort parameter
+// stride, images at the cohort image stride (nullable), loss words loss_acc[M] (nullable), one ``anchor`` [P] for all.
+ECG_API int ecg_slab_reduce_cohort_prox_sgd(const float* slab, int G, int M, int stride, int P, float* params,
+                                            float* mom, float* loss_acc, float lr, float momentum, float wd,
+                                            int nesterov, void* wprep, const float* anchor, float mu,
+                                            hipStream_t stream) {
+  if (!slab || M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
+  return cohort_reduce_dispatch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov,
+                                static_cast<unsigned char*>(wprep), stream, nullptr, anchor, mu, true);
 }
 
 // A local round: ``steps`` times "step kernel, then reduce + SGD kernel" (DP-SGD: step kernel, clip factors, clipped
@@ -1999,8 +2009,6 @@ static void gather_read(StepArgs& a, const GatherArgs& ga, const GatherBufs& g, 
 // FedProx with a snapshot adds one launch per round in front.
 // (Warm-up loads of the next step's windows in the step kernel's tail measured neutral - 11.11 vs 11.08 us/step,
 // the windows already sit in the Infinity Cache; profiles/r2/bench_prefetch.txt - and were removed.)
-static int prox_snapshot_launch(const float* params, float* anchor, int P, hipStream_t stream);  // (end of the file)
-
 static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
   const int P = make_layout(r.nc).P;
   if (r.prox_mu > 0.f && r.prox_snapshot) {
@@ -2148,12 +2156,9 @@ ECG_API int ecg_tiny_cohort_wprep_stride(void) { return kCohortWprepStride; }
 // like a packed EcgTinyRound - the first step builds its operands in LDS, later steps read the images and the packed
 // rows gathered by the previous reduce - and need wprep, xg, yg and xbg, sized for M * B rows
 // (ecg_tiny_gather_floats / _halfs(L, M * B)); fp32 rounds take none of them.  There is no DP-SGD in a cohort.
-// Client-level DP (cdp_clip > 0) and a server step size other than 1 replace the mean by the DP close
-// (cohort_delta_scale_kernel + cohort_dp_mean_kernel); with the cdp_* fields and server_lr all zero the round issues the
-// launches it always issued, cohort_mean_kernel included.  A server optimizer (server_opt != 0) closes the round with
-// cohort_delta_scale_kernel + cohort_server_opt_kernel; with server_opt == 0 the close is the one it was.  With
-// ``server_delta`` the round stops where the delta exists (cohort_delta_scale_kernel + cohort_delta_kernel) and leaves
-// the server step to the caller (ecg_server_opt_step, after an all-reduce of the ranks' deltas).
+// The close: with the cdp_* fields, server_lr, server_opt and server_delta all zero (server_lr 1 counts as zero) it is
+// cohort_mean_kernel; anything else is ecg::tiny::cohort_close (include/tiny_ecg_close.h), which picks its kernel by
+// server_delta, then server_opt.
 // ops/_lib.py mirrors this struct (TinyCohortRound) and checks its size against ecg_tiny_cohort_round_sizeof().
 struct EcgTinyCohortRound {
   const float* X;
@@ -2203,68 +2208,18 @@ struct EcgTinyCohortRound {
 
 ECG_API int ecg_tiny_cohort_round_sizeof(void) { return (int)sizeof(EcgTinyCohortRound); }
 
-namespace {
-
-// (The cohort kernels - MODE 3 and slab_reduce_cohort_sgd_kernel - are first named here, behind every older launch
-// site, so that they are instantiated last.)
-// The cohort forms of the three kernels a production round launches: fp32; bf16 building its operands in LDS (a
-// round's first step: ``a.wprep`` null); bf16 on packed rows and the images (``a.packed``).  Arguments are checked
-// by check_cohort_round.
-int cohort_step_dispatch(int prec, const StepArgs& a, int M, hipStream_t stream) {
-  const bool w8 = pick_waves(a.L, prec == 1) == 8;
-  if (prec == 1)
-    return w8 ? launch_step<8, 3, true, false>(a, stream, M) : launch_step<16, 3, true, false>(a, stream, M);
-  if (a.packed)
-    return w8 ? launch_step<8, 3, false, true, true>(a, stream, M) : launch_step<16, 3, false, true, true>(a, stream, M);
-  if (a.wprep) return ecg::kBadArg;  // the unpacked prepared-fragment kernel has no cohort form
-  return w8 ? launch_step<8, 3, false, false>(a, stream, M) : launch_step<16, 3, false, false>(a, stream, M);
-}
-
-// The cohort reduce + SGD of one step: M x the plain reduce's blocks, then the gather blocks of the next step.
-int cohort_prox_reduce_launch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
-                              float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
-                              const float* anchor, float mu, hipStream_t stream, const GatherArgs* gather);  // (end)
-int cohort_reduce_dispatch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
-                           float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
-                           hipStream_t stream, const GatherArgs* gather = nullptr, const float* anchor = nullptr,
-                           float mu = 0.f) {
-  if (mu != 0.f)  // FedProx: the prox kernel, one anchor for all M clients; mu == 0: the launch it always was
-    return cohort_prox_reduce_launch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov, wprep,
-                                     anchor, mu, stream, gather);
-  const int st = check_reduce(G, stride, P, 1, params, momentum, mom);
-  if (st) return st;
-  const RedGeom g = red_geom(P, M, gather, true);
-  hipLaunchKernelGGL(slab_reduce_cohort_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
-                     params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc, g.ga);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-}  // namespace
-
-// The DP close runs in place of the mean: with a clip norm, or with a server step size other than 1 (0 means 1).
+// A close with a server step runs in place of the mean: with a clip norm, with a server step size other than 1 (0
+// means 1), or with a server optimizer.
 static bool cohort_dp_on(const EcgTinyCohortRound& r) {
   return r.cdp_clip > 0.f || (r.server_lr != 0.f && r.server_lr != 1.f) || r.server_opt != 0;
 }
 
-// defined at the end of the file: the kernels it names are then instantiated behind cohort_mean_kernel
-static int cohort_dp_close_dispatch(const float* params, float* global_params, int P, int M, float clip, float sigma,
-                                    float server_lr, unsigned long long seed, unsigned long long* round_word,
-                                    float* scale, float* norm, hipStream_t stream);
-
-// A server optimizer (server_opt != 0) closes the round with cohort_server_opt_kernel in place of cohort_dp_mean_kernel;
-// both defined at the end of the file, like the DP close.
-static int check_server_opt(int opt, float b1, float b2, float tau, const float* m, const float* v);
-static int cohort_server_close_dispatch(const float* params, float* global_params, int P, int M, float clip,
-                                        float sigma, float server_lr, unsigned long long seed,
-                                        unsigned long long* round_word, float* scale, float* norm, int opt, float b1,
-                                        float b2, float tau, float* m, float* v, hipStream_t stream);
-
-// The split close (server_delta != nullptr): cohort_delta_scale_kernel + cohort_delta_kernel, defined at the end of the
-// file behind the server optimizers' kernels.
-static int cohort_delta_close_dispatch(const float* params, const float* global_params, int P, int M, float clip,
-                                       float sigma, unsigned long long seed, unsigned long long* round_word,
-                                       float* scale, float* norm, float* delta, hipStream_t stream);
+// The round's close as ecg::tiny::cohort_close takes it.
+static CohortClose cohort_close_args(const EcgTinyCohortRound& r) {
+  return {r.params,   r.global_params, make_layout(r.nc).P, r.M,           r.cdp_clip,    r.cdp_sigma,
+          r.server_lr, r.cdp_seed,     r.cdp_round,         r.cdp_scale,   r.cdp_norm,    r.server_opt,
+          r.server_beta1, r.server_beta2, r.server_tau,     r.server_m,    r.server_v,    r.server_delta};
+}
 
 static int check_cohort_round(const EcgTinyCohortRound* r) {
   if (!r || r->steps < 1 || r->M < 1 || r->M > 65535) return ecg::kBadArg;  // (M is the grid's y extent)
@@ -2278,14 +2233,10 @@ static int check_cohort_round(const EcgTinyCohortRound* r) {
   // the slab and gather buffer resources hold byte sizes in 32 bits, and their row offsets are ints
   const long rows = (long)r->M * r->B;
   if (rows * r->slab_stride * 4 > INT_MAX || rows * (pack_ldb(r->L) + 8) * 4 > INT_MAX) return ecg::kTooLarge;
-  if (r->cdp_clip < 0.f || r->cdp_sigma < 0.f || r->server_lr < 0.f) return ecg::kBadArg;
   if (r->prox_mu < 0.f) return ecg::kBadArg;
-  if (r->cdp_sigma > 0.f && r->cdp_clip == 0.f) return ecg::kBadArg;
-  if (cohort_dp_on(*r) && (!r->cdp_scale || !r->cdp_norm || !r->cdp_round)) return ecg::kBadArg;
-  if (r->server_delta) return (!r->cdp_scale || !r->cdp_norm || !r->cdp_round) ? ecg::kBadArg : ecg::kOk;
-  if (r->server_opt != 0)
-    return check_server_opt(r->server_opt, r->server_beta1, r->server_beta2, r->server_tau, r->server_m, r->server_v);
-  return ecg::kOk;
+  if (cohort_dp_on(*r) || r->server_delta) return check_cohort_close(cohort_close_args(*r));
+  // the plain mean reads none of the close's fields; a negative clip norm, or noise without a clip norm, is an error
+  return (r->cdp_clip < 0.f || r->cdp_sigma != 0.f) ? ecg::kBadArg : ecg::kOk;
 }
 
 static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream) {
@@ -2314,16 +2265,7 @@ static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream)
                                 r.nesterov, wprep, stream, gather_next ? &ga : nullptr, r.global_params, r.prox_mu);
     if (st) return st;
   }
-  if (r.server_delta)
-    return cohort_delta_close_dispatch(r.params, r.global_params, P, r.M, r.cdp_clip, r.cdp_sigma, r.cdp_seed,
-                                       r.cdp_round, r.cdp_scale, r.cdp_norm, r.server_delta, stream);
-  if (r.server_opt != 0)
-    return cohort_server_close_dispatch(r.params, r.global_params, P, r.M, r.cdp_clip, r.cdp_sigma, r.server_lr,
-                                        r.cdp_seed, r.cdp_round, r.cdp_scale, r.cdp_norm, r.server_opt, r.server_beta1,
-                                        r.server_beta2, r.server_tau, r.server_m, r.server_v, stream);
-  if (cohort_dp_on(r))
-    return cohort_dp_close_dispatch(r.params, r.global_params, P, r.M, r.cdp_clip, r.cdp_sigma, r.server_lr, r.cdp_seed,
-                                    r.cdp_round, r.cdp_scale, r.cdp_norm, stream);
+  if (cohort_dp_on(r) || r.server_delta) return cohort_close(cohort_close_args(r), stream);
   hipLaunchKernelGGL(cohort_mean_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, r.params, r.global_params,
                      P, r.M, 1.0f / (float)r.M);
   ECG_HIP_CHECK(hipGetLastError());
@@ -2341,384 +2283,4 @@ ECG_API int ecg_tiny_cohort_round_capture(void** handle, const EcgTinyCohortRoun
   const int st = check_cohort_round(round);
   if (st) return st;
   return capture_round(handle, round->steps, [&](hipStream_t cap) { return enqueue_cohort_round(*round, cap); });
-}
-
-// ---------------------------------------------------------------------------- client-level DP close
-// The two launches of the DP close (kept as two: the clip factors need every client's whole delta before any
-// parameter can be written, and a single launch would need a grid-wide barrier for nothing - the pair costs one launch
-// boundary per round).  clip == 0: no clipping (every factor is 1; the norms are still reported); server_lr == 0
-// means 1.  nu = sigma * clip / M is computed in double and rounded to fp32 here; ``sigma`` arrives as an fp32 value
-// (the caller's sigma / sqrt(W), already rounded), so nu can differ by one ulp from the value a caller rounds once
-// from doubles (train/cohort.py does): 2^-24 of the noise, far below the Box-Muller difference between device and host.
-static int cohort_dp_close_dispatch(const float* params, float* global_params, int P, int M, float clip, float sigma,
-                                    float server_lr, unsigned long long seed, unsigned long long* round_word,
-                                    float* scale, float* norm, hipStream_t stream) {
-  const float nu = (float)((double)sigma * (double)clip / (double)M);
-  hipLaunchKernelGGL(cohort_delta_scale_kernel<CDP_CLIENTS_PER_BLOCK>,
-                     dim3((M + CDP_CLIENTS_PER_BLOCK - 1) / CDP_CLIENTS_PER_BLOCK), dim3(CDP_CLIENTS_PER_BLOCK * 64), 0,
-                     stream, params, global_params, P, M, clip > 0.f ? clip : FLT_MAX, scale, norm, round_word);
-  ECG_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(cohort_dp_mean_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, params, global_params, P,
-                     M, 1.0f / (float)M, scale, server_lr == 0.f ? 1.f : server_lr, nu, seed, round_word);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-// Only the close of a cohort round, on caller-supplied buffers: ``params`` holds M clients' weights at the cohort
-// stride (ecg_tiny_cohort_param_stride(nc)), ``global`` [P] the round's starting weights and, afterwards, the new
-// ones; ``scale`` / ``norm`` [M] receive the clip factors and delta norms; the noise is that of round ``round_word[0]``
-// as found, and the word is advanced by one.  ``sigma`` is the noise multiplier of this rank's share, as
-// EcgTinyCohortRound's cdp_sigma.
-ECG_API int ecg_cohort_dp_close(const float* params, float* global, int nc, int M, float clip, float sigma,
-                                float server_lr, unsigned long long seed, unsigned long long* round_word, float* scale,
-                                float* norm, hipStream_t stream) {
-  if (!params || !global || !round_word || !scale || !norm || nc < 1 || nc > MAX_CLASSES) return ecg::kBadArg;
-  if (M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
-  if (clip < 0.f || sigma < 0.f || server_lr < 0.f || (sigma > 0.f && clip == 0.f)) return ecg::kBadArg;
-  return cohort_dp_close_dispatch(params, global, make_layout(nc).P, M, clip, sigma, server_lr, seed, round_word, scale,
-                                  norm, stream);
-}
-
-// Diagnostic: z[0:P], the standard normals the DP close draws for (seed, round r).
-ECG_API int ecg_cohort_dp_noise(float* z, int P, unsigned long long seed, unsigned long long r, hipStream_t stream) {
-  if (!z || P <= 0) return ecg::kBadArg;
-  hipLaunchKernelGGL(cohort_dp_noise_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, z, P, seed, r);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-// ---------------------------------------------------------------------------- server optimizers (FedOpt close)
-// The close of a cohort round with a server optimizer (Reddi et al., "Adaptive Federated Optimization"), in place of
-// cohort_dp_mean_kernel: Delta_i is formed exactly as there - the clipped client deltas in ascending order times
-// inv_M, plus nu * z_i drawn on stream word 1 for round ``round_word[0] - 1`` - and then, with the server state m, v
-// [P] (fp32, kept across rounds; no bias correction, as in the paper) and one_minus = 1 - beta in fp32,
-//   OPT 1 sgdm (FedAvgM):  m = b1 m + Delta;               g += eta m
-//   OPT 2 adagrad:         m = b1 m + (1 - b1) Delta;      v = v + Delta^2
-//   OPT 3 adam:            m as adagrad;                   v = b2 v + (1 - b2) Delta^2
-//   OPT 4 yogi:            m as adagrad;                   v = v - (1 - b2) Delta^2 sign(v - Delta^2), sign(0) = 0
-//   OPT 2..4:              g += eta m / (sqrt(v) + tau)    (the new m and v; division and sqrt correctly rounded)
-// One thread per parameter reads g[i], m[i], v[i] and the M client values and writes g[i], m[i] and (OPT 2..4) v[i]:
-// no atomics, a fixed order.  sgdm takes v == nullptr.  With b1 == 0 and m == 0 sgdm is cohort_dp_mean_kernel's result
-// bit for bit (m = Delta, g + eta * Delta).  (Defined and first named here, behind every older kernel.)
-namespace {
-
-constexpr int SOPT_SGDM = 1, SOPT_ADAGRAD = 2, SOPT_ADAM = 3, SOPT_YOGI = 4;
-
-template <int NT, int OPT>
-__global__ __launch_bounds__(NT) void cohort_server_opt_kernel(
-    const float* __restrict__ params, float* __restrict__ global_params, int P, int M, float inv_M,
-    const float* __restrict__ scale, float server_lr, float noise_scale, unsigned long long seed,
-    const unsigned long long* __restrict__ round_word, float b1, float b2, float tau, float* __restrict__ m,
-    float* __restrict__ v) {
-  const int i = blockIdx.x * NT + threadIdx.x;
-  if (i >= P) return;
-  const int pstride = cohort_pstride(P);
-  float noise = 0.f;
-  if (noise_scale != 0.f) noise = noise_scale * cohort_dp_normal(i, seed, round_word[0] - 1ull);
-  const float g = global_params[i];
-  const float m0 = m[i];
-  float v1 = 0.f;
-  if (OPT != SOPT_SGDM) v1 = v[i];
-  // The fused multiply-adds of Delta and of the sgdm step are written out: they are what cohort_dp_mean_kernel's
-  // expressions contract to, and left to the compiler b1 * m0 and s * inv_M pair up in one packed multiply, which
-  // rounds Delta once more than that kernel does.
-  float s = scale[0] * (params[i] - g);
-  for (int c = 1; c < M; ++c) s = __builtin_fmaf(scale[c], params[(long)c * pstride + i] - g, s);
-  const float delta = __builtin_fmaf(s, inv_M, noise);
-  float m1;
-  if (OPT == SOPT_SGDM) {
-    m1 = __builtin_fmaf(b1, m0, delta);
-    global_params[i] = __builtin_fmaf(server_lr, m1, g);
-  } else {
-    m1 = b1 * m0 + (1.f - b1) * delta;
-    const float d2 = delta * delta;
-    if (OPT == SOPT_ADAGRAD) {
-      v1 = v1 + d2;
-    } else if (OPT == SOPT_ADAM) {
-      v1 = b2 * v1 + (1.f - b2) * d2;
-    } else {
-      const float e = v1 - d2;
-      const float sg = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
-      v1 = v1 - (1.f - b2) * d2 * sg;
-    }
-    v[i] = v1;
-    global_params[i] = g + (server_lr * m1) / (sqrtf(v1) + tau);
-  }
-  m[i] = m1;
-}
-
-}  // namespace
-
-static int check_server_opt(int opt, float b1, float b2, float tau, const float* m, const float* v) {
-  if (opt < SOPT_SGDM || opt > SOPT_YOGI || !m) return ecg::kBadArg;
-  if (!(b1 >= 0.f && b1 < 1.f) || !(b2 >= 0.f && b2 < 1.f)) return ecg::kBadArg;
-  if (opt != SOPT_SGDM && (!v || !(tau > 0.f))) return ecg::kBadArg;
-  return ecg::kOk;
-}
-
-// The two launches of the close with a server optimizer: cohort_delta_scale_kernel as in the DP close (it advances the
-// round word and reports the norms), then cohort_server_opt_kernel in place of cohort_dp_mean_kernel - two launches for
-// the reason given at cohort_dp_close_dispatch.  clip, sigma, server_lr and nu as there.
-static int cohort_server_close_dispatch(const float* params, float* global_params, int P, int M, float clip,
-                                        float sigma, float server_lr, unsigned long long seed,
-                                        unsigned long long* round_word, float* scale, float* norm, int opt, float b1,
-                                        float b2, float tau, float* m, float* v, hipStream_t stream) {
-  const int st = check_server_opt(opt, b1, b2, tau, m, v);
-  if (st) return st;
-  const float nu = (float)((double)sigma * (double)clip / (double)M);
-  const float eta = server_lr == 0.f ? 1.f : server_lr, inv_M = 1.0f / (float)M;
-  hipLaunchKernelGGL(cohort_delta_scale_kernel<CDP_CLIENTS_PER_BLOCK>,
-                     dim3((M + CDP_CLIENTS_PER_BLOCK - 1) / CDP_CLIENTS_PER_BLOCK), dim3(CDP_CLIENTS_PER_BLOCK * 64), 0,
-                     stream, params, global_params, P, M, clip > 0.f ? clip : FLT_MAX, scale, norm, round_word);
-  ECG_HIP_CHECK(hipGetLastError());
-  const dim3 grid((P + 255) / 256), block(256);
-  const unsigned long long* word = round_word;
-#define ECG_SERVER_OPT_LAUNCH(OPT)                                                                                   \
-  hipLaunchKernelGGL((cohort_server_opt_kernel<256, OPT>), grid, block, 0, stream, params, global_params, P, M, inv_M, \
-                     (const float*)scale, eta, nu, seed, word, b1, b2, tau, m, v)
-  switch (opt) {
-    case SOPT_SGDM: ECG_SERVER_OPT_LAUNCH(SOPT_SGDM); break;
-    case SOPT_ADAGRAD: ECG_SERVER_OPT_LAUNCH(SOPT_ADAGRAD); break;
-    case SOPT_ADAM: ECG_SERVER_OPT_LAUNCH(SOPT_ADAM); break;
-    default: ECG_SERVER_OPT_LAUNCH(SOPT_YOGI); break;
-  }
-#undef ECG_SERVER_OPT_LAUNCH
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-// ecg_cohort_dp_close's twin with a server optimizer: the same buffers and meaning of clip, sigma, server_lr, seed and
-// the round word, plus ``opt`` (1 sgdm, 2 adagrad, 3 adam, 4 yogi), beta1, beta2 in [0, 1), tau > 0 (opt 2..4) and the
-// server state ``m`` / ``v`` [P], read and written (``v`` may be null for sgdm).
-ECG_API int ecg_cohort_server_close(const float* params, float* global, int nc, int M, float clip, float sigma,
-                                    float server_lr, unsigned long long seed, unsigned long long* round_word,
-                                    float* scale, float* norm, int opt, float b1, float b2, float tau, float* m,
-                                    float* v, hipStream_t stream) {
-  if (!params || !global || !round_word || !scale || !norm || nc < 1 || nc > MAX_CLASSES) return ecg::kBadArg;
-  if (M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
-  if (clip < 0.f || sigma < 0.f || server_lr < 0.f || (sigma > 0.f && clip == 0.f)) return ecg::kBadArg;
-  return cohort_server_close_dispatch(params, global, make_layout(nc).P, M, clip, sigma, server_lr, seed, round_word,
-                                      scale, norm, opt, b1, b2, tau, m, v, stream);
-}
-
-// ---------------------------------------------------------------------------- the split close (global server step)
-// The closes above take the server step on this rank's delta.  A driver of several ranks that wants ONE server
-// optimizer over all their clients must average the deltas first (the adaptive rules are nonlinear in Delta), so the
-// close is split where Delta exists: cohort_delta_kernel ends the round with Delta in a buffer of its own, the caller
-// all-reduces that buffer, and server_step_kernel takes the step every rank then takes alike.  Run back to back on one
-// rank the pair leaves the bits of the fused close.  (Defined and first named here, behind every older kernel.)
-namespace {
-
-// delta[i] = Delta_i, bit for bit the value cohort_dp_mean_kernel and cohort_server_opt_kernel form (the fused
-// multiply-adds written out, as in the latter and for the reason given there); nothing else is written, and exactly P
-// floats of a client are read.
-template <int NT>
-__global__ __launch_bounds__(NT) void cohort_delta_kernel(
-    const float* __restrict__ params, const float* __restrict__ global_params, int P, int M, float inv_M,
-    const float* __restrict__ scale, float noise_scale, unsigned long long seed,
-    const unsigned long long* __restrict__ round_word, float* __restrict__ delta) {
-  const int i = blockIdx.x * NT + threadIdx.x;
-  if (i >= P) return;
-  const int pstride = cohort_pstride(P);
-  float noise = 0.f;
-  if (noise_scale != 0.f) noise = noise_scale * cohort_dp_normal(i, seed, round_word[0] - 1ull);
-  const float g = global_params[i];
-  float s = scale[0] * (params[i] - g);
-  for (int c = 1; c < M; ++c) s = __builtin_fmaf(scale[c], params[(long)c * pstride + i] - g, s);
-  delta[i] = __builtin_fmaf(s, inv_M, noise);
-}
-
-// One server step on a flat vector of n floats: OPT 0 the plain step g = fma(eta, delta, g) (m and v not touched), OPT
-// 1..4 cohort_server_opt_kernel's rules from Delta on.  Every rounding is pinned - contraction is off in the body and
-// the fused multiply-adds are written out - to what cohort_dp_mean_kernel and cohort_server_opt_kernel compile to, so
-// that the split close ends on their bits: sgdm's two fused multiply-adds, adagrad's v = fma(Delta, Delta, v), yogi's
-// sign taken of fma(-Delta, Delta, v), every other product and sum rounded on its own.  Division and sqrtf are
-// correctly rounded; one thread per element, no atomics.
-template <int NT, int OPT>
-__global__ __launch_bounds__(NT) void server_step_kernel(float* __restrict__ g, const float* __restrict__ delta, long n,
-                                                         float eta, float b1, float b2, float tau,
-                                                         float* __restrict__ m, float* __restrict__ v) {
-#pragma clang fp contract(off)
-  const long i = (long)blockIdx.x * NT + threadIdx.x;
-  if (i >= n) return;
-  const float d = delta[i], g0 = g[i];
-  if (OPT == 0) {
-    g[i] = __builtin_fmaf(eta, d, g0);
-    return;
-  }
-  const float m0 = m[i];
-  float m1;
-  if (OPT == SOPT_SGDM) {
-    m1 = __builtin_fmaf(b1, m0, d);
-    g[i] = __builtin_fmaf(eta, m1, g0);
-  } else {
-    float v1 = v[i];
-    m1 = b1 * m0 + (1.f - b1) * d;
-    if (OPT == SOPT_ADAGRAD) {
-      v1 = __builtin_fmaf(d, d, v1);
-    } else if (OPT == SOPT_ADAM) {
-      v1 = b2 * v1 + (1.f - b2) * (d * d);
-    } else {
-      const float e = __builtin_fmaf(-d, d, v1);
-      const float sg = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
-      v1 = v1 - ((1.f - b2) * (d * d)) * sg;
-    }
-    v[i] = v1;
-    g[i] = g0 + (eta * m1) / (sqrtf(v1) + tau);
-  }
-  m[i] = m1;
-}
-
-}  // namespace
-
-// The two launches of the split close: cohort_delta_scale_kernel as in the other closes (it advances the round word
-// and reports the norms and factors), then cohort_delta_kernel.  clip, sigma and nu as at cohort_dp_close_dispatch.
-static int cohort_delta_close_dispatch(const float* params, const float* global_params, int P, int M, float clip,
-                                       float sigma, unsigned long long seed, unsigned long long* round_word,
-                                       float* scale, float* norm, float* delta, hipStream_t stream) {
-  const float nu = (float)((double)sigma * (double)clip / (double)M);
-  hipLaunchKernelGGL(cohort_delta_scale_kernel<CDP_CLIENTS_PER_BLOCK>,
-                     dim3((M + CDP_CLIENTS_PER_BLOCK - 1) / CDP_CLIENTS_PER_BLOCK), dim3(CDP_CLIENTS_PER_BLOCK * 64), 0,
-                     stream, params, global_params, P, M, clip > 0.f ? clip : FLT_MAX, scale, norm, round_word);
-  ECG_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(cohort_delta_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, params, global_params, P, M,
-                     1.0f / (float)M, (const float*)scale, nu, seed, (const unsigned long long*)round_word, delta);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-// ecg_cohort_dp_close's twin that stops at the delta: the same buffers and meaning of clip, sigma, seed and the round
-// word; ``global`` [P] is only read, ``delta`` [P] receives the averaged, clipped, noised delta.
-ECG_API int ecg_cohort_delta_close(const float* params, const float* global, int nc, int M, float clip, float sigma,
-                                   unsigned long long seed, unsigned long long* round_word, float* scale, float* norm,
-                                   float* delta, hipStream_t stream) {
-  if (!params || !global || !round_word || !scale || !norm || !delta || nc < 1 || nc > MAX_CLASSES)
-    return ecg::kBadArg;
-  if (M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
-  if (clip < 0.f || sigma < 0.f || (sigma > 0.f && clip == 0.f)) return ecg::kBadArg;
-  return cohort_delta_close_dispatch(params, global, make_layout(nc).P, M, clip, sigma, seed, round_word, scale, norm,
-                                     delta, stream);
-}
-
-// One server step on ``g`` [n] from ``delta`` [n] (the second half of the split close, after the caller averaged the
-// ranks' deltas): ``opt`` 0 the plain step g += eta delta (m and v are not read and may be null), 1 sgdm, 2 adagrad, 3
-// adam, 4 yogi with the server state ``m`` / ``v`` [n], read and written (``v`` may be null for sgdm); eta == 0 means
-// 1; beta1, beta2 in [0, 1) and tau > 0 as in check_server_opt.
-ECG_API int ecg_server_opt_step(float* g, const float* delta, long n, int opt, float eta, float b1, float b2, float tau,
-                                float* m, float* v, hipStream_t stream) {
-  if (!g || !delta || n < 1 || eta < 0.f) return ecg::kBadArg;
-  if (opt != 0) {
-    const int st = check_server_opt(opt, b1, b2, tau, m, v);
-    if (st) return st;
-  }
-  if ((n + 255) / 256 > (long)INT_MAX) return ecg::kTooLarge;
-  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  const float step = eta == 0.f ? 1.f : eta;
-#define ECG_SERVER_STEP_LAUNCH(OPT) \
-  hipLaunchKernelGGL((server_step_kernel<256, OPT>), grid, block, 0, stream, g, delta, n, step, b1, b2, tau, m, v)
-  switch (opt) {
-    case 0: ECG_SERVER_STEP_LAUNCH(0); break;
-    case SOPT_SGDM: ECG_SERVER_STEP_LAUNCH(SOPT_SGDM); break;
-    case SOPT_ADAGRAD: ECG_SERVER_STEP_LAUNCH(SOPT_ADAGRAD); break;
-    case SOPT_ADAM: ECG_SERVER_STEP_LAUNCH(SOPT_ADAM); break;
-    default: ECG_SERVER_STEP_LAUNCH(SOPT_YOGI); break;
-  }
-#undef ECG_SERVER_STEP_LAUNCH
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-// ---------------------------------------------------------------------------- FedProx (proximal local steps)
-// slab_reduce_body's PROX form in the plain and the cohort kernel, and the snapshot a single client's round starts
-// with.  The step kernel is not involved: the proximal term only enters the SGD epilogue, as one more load per updating
-// thread (under the slab reads) and a subtract and a multiply-add.  (Defined and first named here, behind every older
-// kernel.)
-namespace {
-
-// The plain kernel's argument order with ``anchor``, ``mu`` in front of ``ga``.
-template <int RED_COLS>
-__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_prox_sgd_kernel(
-    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
-    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
-    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, float* __restrict__ grad_out,
-    const float* __restrict__ anchor, float mu, GatherArgs ga) {
-  slab_reduce_body<RED_COLS, false, false, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
-                                                 loss_acc, grad_out, nullptr, 0.f, 0ull, nullptr, ga, anchor, mu);
-}
-
-// The cohort kernel's argument order with ``anchor`` [P] - one vector for all M clients - and ``mu`` in front of ``ga``.
-template <int RED_COLS>
-__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_prox_sgd_kernel(
-    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
-    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
-    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, const float* __restrict__ anchor, float mu,
-    GatherArgs ga) {
-  slab_reduce_body<RED_COLS, false, true, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
-                                                loss_acc, nullptr, nullptr, 0.f, 0ull, nullptr, ga, anchor, mu);
-}
-
-// anchor[0:P] = params[0:P]: the first launch of a single client's FedProx round.
-template <int NT>
-__global__ __launch_bounds__(NT) void prox_snapshot_kernel(const float* __restrict__ params, float* __restrict__ anchor,
-                                                           int P) {
-  const int i = blockIdx.x * NT + threadIdx.x;
-  if (i < P) anchor[i] = params[i];
-}
-
-int prox_reduce_launch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
-                       float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
-                       unsigned char* wprep, const float* anchor, float mu, hipStream_t stream,
-                       const GatherArgs* gather) {
-  int st = check_reduce(G, stride, P, apply, params, momentum, mom);
-  if (!st) st = check_prox(anchor, mu);
-  if (st) return st;
-  const RedGeom g = red_geom(P, 1, gather);
-  hipLaunchKernelGGL(slab_reduce_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
-                     params, mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc,
-                     grad_out, anchor, mu, g.ga);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-int cohort_prox_reduce_launch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
-                              float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
-                              const float* anchor, float mu, hipStream_t stream, const GatherArgs* gather) {
-  int st = check_reduce(G, stride, P, 1, params, momentum, mom);
-  if (!st) st = check_prox(anchor, mu);
-  if (st) return st;
-  const RedGeom g = red_geom(P, M, gather, true);
-  hipLaunchKernelGGL(slab_reduce_cohort_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream,
-                     slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
-                     anchor, mu, g.ga);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-}  // namespace
-
-static int prox_snapshot_launch(const float* params, float* anchor, int P, hipStream_t stream) {
-  hipLaunchKernelGGL(prox_snapshot_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, params, anchor, P);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-// ecg_slab_reduce_sgd with the proximal term mu * (p - anchor[col]) in the gradient (``anchor`` [P], mu >= 0).  It
-// always launches the prox kernel: mu == 0 gives ecg_slab_reduce_sgd's bits.
-ECG_API int ecg_slab_reduce_prox_sgd(const float* slab, int G, int stride, int P, float* params, float* mom,
-                                     float* grad_out, float* loss_acc, float lr, float momentum, float wd, int nesterov,
-                                     int apply, void* wprep, const float* anchor, float mu, hipStream_t stream) {
-  if (wprep && !apply) return ecg::kBadArg;
-  return prox_reduce_launch(slab, G, stride, P, params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply,
-                            static_cast<unsigned char*>(wprep), anchor, mu, stream, nullptr);
-}
-
-// The cohort twin on caller-supplied buffers: M clients' G slab rows each, weights / momenta at the cohort parameter
-// stride, images at the cohort image stride (nullable), loss words loss_acc[M] (nullable), one ``anchor`` [P] for all.
-ECG_API int ecg_slab_reduce_cohort_prox_sgd(const float* slab, int G, int M, int stride, int P, float* params,
-                                            float* mom, float* loss_acc, float lr, float momentum, float wd,
-                                            int nesterov, void* wprep, const float* anchor, float mu,
-                                            hipStream_t stream) {
-  if (!slab || M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
-  return cohort_prox_reduce_launch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov,
-                                   static_cast<unsigned char*>(wprep), anchor, mu, stream, nullptr);
 }

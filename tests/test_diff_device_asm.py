@@ -84,6 +84,32 @@ def test_missing_kernel():
     assert not ok and any(line.startswith("MISSING in A") and "_Z2k2Pf" in line for line in report)
 
 
+def test_kernels_moved_to_a_second_file_compare_against_the_union():
+    """``a.hip=b1.hip+b2.hip``: a kernel of A's one file that B defines in its second file is identical; a kernel
+    that both of B's files define is an error."""
+    import pytest
+    assert dda.parse_spec("a.hip") == (["a.hip"], ["a.hip"])
+    assert dda.parse_spec("a.hip=b1.hip+b2.hip") == (["a.hip"], ["b1.hip", "b2.hip"])
+    a = _asm({"_Z2k1Pf": KA, "_Z2k2Pf": KB})
+    b1, b2 = _asm({"_Z2k1Pf": KA}, cuid="1111111111111111"), _asm({"_Z2k2Pf": KB}, cuid="2222222222222222")
+    ok, report = dda.compare([a], [b1, b2])
+    assert ok, report
+    assert sorted(line.split()[1] for line in report if line.startswith("identical")) == ["_Z2k1Pf", "_Z2k2Pf"]
+    assert not any(dda.OUTSIDE in line for line in report)  # one file against two: kernels only
+    # ... which includes a kernel's register figures, written behind its .size
+    assert any(".num_vgpr, 3" in line for line in dda.split_kernels(b2)["_Z2k2Pf"])
+    ok, report = dda.compare([a], [b1, b2.replace("_Z2k2Pf.num_vgpr, 3", "_Z2k2Pf.num_vgpr, 4")])
+    assert not ok and any(line.startswith("DIFFERENT") and "_Z2k2Pf" in line for line in report)
+    # a changed instruction in the moved kernel is still found, and a kernel left behind in neither file is missing
+    b2x = _asm({"_Z2k2Pf": [KB[0], "global_load_dwordx2 v[4:5], v[2:3], off", KB[2]]})
+    ok, report = dda.compare([a], [b1, b2x])
+    assert not ok and any(line.startswith("DIFFERENT") and "_Z2k2Pf" in line for line in report)
+    ok, report = dda.compare([a], [b1, _asm({})])
+    assert not ok and any(line.startswith("MISSING in B") and "_Z2k2Pf" in line for line in report)
+    with pytest.raises(ValueError, match="_Z2k1Pf"):
+        dda.compare([a], [b1, _asm({"_Z2k1Pf": KA, "_Z2k2Pf": KB})])
+
+
 def test_differing_hip_cuid_is_ignored():
     kernels = {"_Z2k1Pf": KA, "_Z2k2Pf": KB}
     ok, report = dda.compare(_asm(kernels, cuid="0123456789abcdef"), _asm(kernels, cuid="fedcba9876543210"))

@@ -20,45 +20,21 @@ import torch.multiprocessing as mp
 import crossscale_ecg  # noqa: F401
 from crossscale_ecg.models.tiny_ecg import TinyECG, num_params
 
+from cohort_harness import DELTA_CANARY, LR, MU, N, WD, Cohort, _clients, _data, _global, _lib, _table
+
 pytestmark = pytest.mark.gpu
 
-N = 64
-LR, MU, WD = 1e-2, 0.9, 1e-3
 EPS32 = 2.0 ** -23
 SEED = 0xC0FFEE1234567
 R0 = (1 << 32) + 3  # a round counter that uses both counter words
 OPTS = {"none": 0, "sgdm": 1, "adagrad": 2, "adam": 3, "yogi": 4}
 B1, B2, TAU = 0.9, 0.99, 1e-3
-CANARY = -777.25
+CANARY = DELTA_CANARY
 BAD = 1  # kBadArg
-
-
-def _lib():
-    from crossscale_ecg.ops import _lib
-    return _lib
 
 
 def _f(x):
     return float(np.float32(x))
-
-
-def _global(nc, seed=1):
-    torch.manual_seed(seed)
-    return torch.cat([p.detach().reshape(-1) for p in TinyECG(num_classes=nc).parameters()]).cuda()
-
-
-def _clients(nc, M, clip, seed=2):
-    """(g [P], params [M, pstride]): client c ends on g + d_c with |d_c| = 4 C, C / 2, 0 for c % 3 = 0, 1, 2; the
-    pstride - P padding floats are NaN (a kernel that read them into a result would return NaN)."""
-    P, ps = num_params(nc), _lib().kernels().ecg_tiny_cohort_param_stride(nc)
-    g = _global(nc)
-    gen = torch.Generator().manual_seed(seed)
-    d = torch.randn(M, P, generator=gen, dtype=torch.float64)
-    target = torch.tensor([[4 * clip, clip / 2, 0.0][c % 3] for c in range(M)], dtype=torch.float64)
-    d = d * (target / d.norm(dim=1))[:, None]
-    params = torch.full((M, ps), float("nan"), dtype=torch.float32, device="cuda")
-    params[:, :P] = (g.double().cpu()[None, :] + d).float().cuda()
-    return g, params
 
 
 def _step(g, delta, n, opt, eta, m, v, b1=B1, b2=B2, tau=TAU):
@@ -194,83 +170,6 @@ def test_server_opt_step_odd_sizes_against_float64(n):
 
 
 # ------------------------------------------------------------------------------------------------------ whole rounds
-def _data(L, nc, seed=0):
-    dev = torch.device("cuda:0")
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(N, L, generator=g).to(dev)
-    y32 = torch.randint(0, nc, (N,), generator=g).to(torch.int32).to(dev)
-    return dev, x, y32
-
-
-def _table(S, rows, seed=2):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(0, N, (S, rows), generator=g).to(torch.int32).cuda()
-
-
-class Cohort:
-    """The buffers of one native cohort round with a fan-out.  ``dp`` (dict of cdp_clip, cdp_sigma, server_lr, cdp_seed,
-    round) adds the client-DP fields and buffers, ``so`` (dict of server_opt, server_beta1, server_beta2, server_tau) the
-    server optimizer's with m = 0 and v = tau^2, ``split`` a ``server_delta`` buffer with a canary behind it; what is
-    None or False is not named when the struct is built."""
-
-    def __init__(self, x, y32, nc, M, B, S, precision, table, glob, dp=None, so=None, split=False):
-        from crossscale_ecg.ops.fused_tiny import prec_id, slab_stride
-        L_ = _lib()
-        lib = L_.kernels()
-        dev, L = x.device, x.shape[1]
-        self.P, self.M = num_params(nc), M
-        ps, ws = lib.ecg_tiny_cohort_param_stride(nc), lib.ecg_tiny_cohort_wprep_stride()
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.cparams, self.cmom = torch.zeros((M, ps), **f32), torch.zeros((M, ps), **f32)
-        self.glob = glob.clone()
-        self.slab = torch.zeros((M * B, slab_stride(nc)), **f32)
-        self.loss = torch.zeros(M, **f32)
-        self.table = table
-        self.wprep = self.xg = self.yg = self.xbg = None
-        if precision == "bf16":
-            self.wprep = torch.zeros(M * ws, dtype=torch.uint8, device=dev)
-            self.xg = torch.zeros(lib.ecg_tiny_gather_floats(L, M * B), **f32)
-            self.yg = torch.zeros(2 * M * B, dtype=torch.int32, device=dev)
-            self.xbg = torch.zeros(lib.ecg_tiny_gather_halfs(L, M * B), dtype=torch.bfloat16, device=dev)
-        p = L_.ptr
-        kw = {}
-        self.scale = self.norm = self.word = self.m = self.v = self.delta = None
-        if dp is not None:
-            self.scale, self.norm = torch.full((M,), -1.0, **f32), torch.full((M,), -1.0, **f32)
-            self.word = torch.tensor([dp["round"]], dtype=torch.int64, device=dev)
-            kw = dict(cdp_clip=dp["cdp_clip"], cdp_sigma=dp["cdp_sigma"], server_lr=dp["server_lr"],
-                      cdp_seed=dp["cdp_seed"], cdp_scale=self.scale.data_ptr(), cdp_norm=self.norm.data_ptr(),
-                      cdp_round=self.word.data_ptr())
-        if so is not None:
-            self.m = torch.zeros(self.P, **f32)
-            if so["server_opt"] != 1:
-                self.v = torch.full((self.P,), so["server_tau"], **f32) ** 2
-            kw.update(so, server_m=self.m.data_ptr(), server_v=p(self.v))
-        if split:
-            self.delta = torch.full((self.P + 8,), CANARY, **f32)
-            kw.update(server_delta=self.delta.data_ptr())
-        self.round = L_.TinyCohortRound(
-            X=x.data_ptr(), ldx=x.stride(0), idx=table.data_ptr(), Y=y32.data_ptr(), params=self.cparams.data_ptr(),
-            mom=self.cmom.data_ptr(), slab=self.slab.data_ptr(), loss_acc=self.loss.data_ptr(), wprep=p(self.wprep),
-            xg=p(self.xg), yg=p(self.yg), xbg=p(self.xbg), global_params=self.glob.data_ptr(), L=L, nc=nc,
-            slab_stride=self.slab.shape[1], B=B, steps=S, M=M, fanout=1, lr=LR, momentum=MU, wd=WD, nesterov=0,
-            prec=prec_id(precision), **kw)
-
-    def enqueue(self):
-        L_ = _lib()
-        return L_.kernels().ecg_tiny_cohort_round_enqueue(C.byref(self.round), L_.stream_ptr(self.glob.device))
-
-    def run(self):
-        _lib().check(self.enqueue(), "ecg_tiny_cohort_round_enqueue")
-        torch.cuda.synchronize()
-        return self
-
-    def state(self):
-        out = [self.glob, self.cparams, self.cmom, self.loss]
-        out += [t for t in (self.wprep, self.scale, self.norm, self.word, self.m, self.v) if t is not None]
-        return [t.clone() for t in out]
-
-
 M_, B_, S_ = 3, 4, 2
 DP = dict(cdp_clip=0.004, cdp_sigma=1.2, server_lr=0.8, cdp_seed=SEED, round=R0)
 

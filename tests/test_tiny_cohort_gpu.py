@@ -13,24 +13,18 @@ import torch
 import crossscale_ecg  # noqa: F401
 from crossscale_ecg.models.tiny_ecg import TinyECG, num_params
 
+import cohort_harness
+from cohort_harness import LR, MU, N, WD, _data, _lib, _table
+
 pytestmark = pytest.mark.gpu
 
-N = 64
-LR, MU, WD = 1e-2, 0.9, 1e-3
 CANARY = 1234.5
 
 
-def _lib():
-    from crossscale_ecg.ops import _lib
-    return _lib
-
-
-def _data(L, nc, seed=0):
-    dev = torch.device("cuda:0")
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(N, L, generator=g).to(dev)
-    y32 = torch.randint(0, nc, (N,), generator=g).to(torch.int32).to(dev)
-    return dev, x, y32
+def Cohort(x, y32, nc, M, B, S, precision, table, w=None, m=None, glob=None, fanout=0, momentum=MU):
+    """The harness's round without a fan-out by default and with the clients' buffers, padding included, on CANARY."""
+    return cohort_harness.Cohort(x, y32, nc, M, B, S, precision, table, glob, fanout=fanout, w=w, m=m,
+                                 momentum=momentum, pad=CANARY)
 
 
 def _weights(nc, M, seed=1):
@@ -42,62 +36,6 @@ def _weights(nc, M, seed=1):
     w = flat[None, :] + 0.05 * torch.randn(M, P, generator=g).cuda()
     m = 0.01 * torch.randn(M, P, generator=g).cuda()
     return flat, w, m
-
-
-def _table(S, rows, seed=2):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(0, N, (S, rows), generator=g).to(torch.int32).cuda()
-
-
-class Cohort:
-    """The buffers of one native cohort round and its ``TinyCohortRound``."""
-
-    def __init__(self, x, y32, nc, M, B, S, precision, table, w=None, m=None, glob=None, fanout=0, momentum=MU):
-        from crossscale_ecg.ops.fused_tiny import prec_id, slab_stride
-        lib = _lib().kernels()
-        dev, L = x.device, x.shape[1]
-        self.P, self.M, self.B, self.S = num_params(nc), M, B, S
-        self.ps, self.ws = lib.ecg_tiny_cohort_param_stride(nc), lib.ecg_tiny_cohort_wprep_stride()
-        self.wp_bytes = lib.ecg_tiny_wprep_bytes()
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.cparams = torch.full((M, self.ps), CANARY, **f32)
-        self.cmom = torch.full((M, self.ps), CANARY, **f32)
-        if w is not None:
-            self.cparams[:, : self.P] = w
-            self.cmom[:, : self.P] = m
-        self.glob = torch.zeros(self.P, **f32) if glob is None else glob.clone()
-        self.slab = torch.zeros((M * B, slab_stride(nc)), **f32)
-        self.loss = torch.zeros(M, **f32)
-        self.table = table
-        self.wprep = self.xg = self.yg = self.xbg = None
-        if precision == "bf16":
-            self.wprep = torch.zeros(M * self.ws, dtype=torch.uint8, device=dev)
-            self.xg = torch.zeros(lib.ecg_tiny_gather_floats(L, M * B), **f32)
-            self.yg = torch.zeros(2 * M * B, dtype=torch.int32, device=dev)
-            self.xbg = torch.zeros(lib.ecg_tiny_gather_halfs(L, M * B), dtype=torch.bfloat16, device=dev)
-        p = _lib().ptr
-        self.round = _lib().TinyCohortRound(
-            X=x.data_ptr(), ldx=x.stride(0), idx=table.data_ptr(), Y=y32.data_ptr(), params=self.cparams.data_ptr(),
-            mom=self.cmom.data_ptr(), slab=self.slab.data_ptr(), loss_acc=self.loss.data_ptr(), wprep=p(self.wprep),
-            xg=p(self.xg), yg=p(self.yg), xbg=p(self.xbg), global_params=self.glob.data_ptr(), L=L, nc=nc,
-            slab_stride=self.slab.shape[1], B=B, steps=S, M=M, fanout=fanout, lr=LR, momentum=momentum, wd=WD,
-            nesterov=0, prec=prec_id(precision))
-
-    def enqueue(self):
-        L = _lib()
-        return L.kernels().ecg_tiny_cohort_round_enqueue(C.byref(self.round), L.stream_ptr(self.glob.device))
-
-    def run(self):
-        _lib().check(self.enqueue(), "ecg_tiny_cohort_round_enqueue")
-        torch.cuda.synchronize()
-        return self
-
-    def image(self, c):
-        return self.wprep[c * self.ws: c * self.ws + self.wp_bytes]
-
-    def state(self):
-        out = [self.glob, self.cparams, self.cmom, self.loss]
-        return [t.clone() for t in out + ([self.wprep] if self.wprep is not None else [])]
 
 
 def _single_round(x, y32, nc, B, S, precision, table_c, w, m, momentum=MU):

@@ -13,18 +13,15 @@ import torch
 import crossscale_ecg  # noqa: F401
 from crossscale_ecg.models.tiny_ecg import TinyECG, num_params
 
+import cohort_harness
+from cohort_harness import N, _global as _flat, _lib as _L, _table
+
 pytestmark = pytest.mark.gpu
 
-N = 64
-LR, MOM, WD, MU = 1e-2, 0.9, 1e-3, 0.1
+LR, MOM, WD, MU = cohort_harness.LR, cohort_harness.MU, cohort_harness.WD, 0.1  # MU: the FedProx coefficient
 GS = [1, 32, 256, 259]
 OPTS = [(0.0, 0, 0.0), (MOM, 0, WD), (MOM, 1, WD)]  # (momentum, nesterov, weight decay)
 BAD = 1  # kBadArg
-
-
-def _L():
-    from crossscale_ecg.ops import _lib
-    return _lib
 
 
 def _stride(nc):
@@ -132,76 +129,13 @@ def test_mu_zero_through_the_prox_kernel_is_the_plain_reduce_bitwise(nc, G, mome
     assert not torch.equal(out[0][0], p0) and bool(out[0][2].any())
 
 
-class Cohort:
-    """The buffers of one native cohort round and its ``TinyCohortRound`` (fp32 or bf16)."""
-
-    def __init__(self, x, y32, nc, M, B, S, precision, table, glob, fanout=1, w=None, m=None, prox_mu=0.0,
-                 with_prox_field=True, pad=0.0, **fields):
-        from crossscale_ecg.ops.fused_tiny import prec_id
-        L_ = _L()
-        lib = L_.kernels()
-        dev, L = x.device, x.shape[1]
-        self.P, self.M, self.B, self.S = num_params(nc), M, B, S
-        self.ps, self.ws = lib.ecg_tiny_cohort_param_stride(nc), lib.ecg_tiny_cohort_wprep_stride()
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.cparams, self.cmom = torch.full((M, self.ps), pad, **f32), torch.full((M, self.ps), pad, **f32)
-        if w is not None:
-            self.cparams[:, :self.P], self.cmom[:, :self.P] = w, m
-        self.glob = glob.clone()
-        self.slab = torch.zeros((M * B, _stride(nc)), **f32)
-        self.loss = torch.zeros(M, **f32)
-        self.table = table
-        self.wprep = self.xg = self.yg = self.xbg = None
-        if precision == "bf16":
-            self.wprep = torch.zeros(M * self.ws, dtype=torch.uint8, device=dev)
-            self.xg = torch.zeros(lib.ecg_tiny_gather_floats(L, M * B), **f32)
-            self.yg = torch.zeros(2 * M * B, dtype=torch.int32, device=dev)
-            self.xbg = torch.zeros(lib.ecg_tiny_gather_halfs(L, M * B), dtype=torch.bfloat16, device=dev)
-        p = L_.ptr
-        kw = dict(X=x.data_ptr(), ldx=x.stride(0), idx=table.data_ptr(), Y=y32.data_ptr(), params=self.cparams.data_ptr(),
-                  mom=self.cmom.data_ptr(), slab=self.slab.data_ptr(), loss_acc=self.loss.data_ptr(), wprep=p(self.wprep),
-                  xg=p(self.xg), yg=p(self.yg), xbg=p(self.xbg), global_params=self.glob.data_ptr(), L=L, nc=nc,
-                  slab_stride=self.slab.shape[1], B=B, steps=S, M=M, fanout=fanout, lr=LR, momentum=MOM, wd=WD,
-                  nesterov=0, prec=prec_id(precision))
-        self.keep = []
-        for k, v in fields.items():  # server optimizer / client-DP buffers (tensors are kept alive here)
-            if isinstance(v, torch.Tensor):
-                self.keep.append(v)
-                v = v.data_ptr()
-            kw[k] = v
-        if with_prox_field:
-            kw["prox_mu"] = prox_mu
-        self.round = L_.TinyCohortRound(**kw)
-
-    def enqueue(self):
-        L_ = _L()
-        return L_.kernels().ecg_tiny_cohort_round_enqueue(C.byref(self.round), L_.stream_ptr(self.glob.device))
-
-    def run(self):
-        _L().check(self.enqueue(), "ecg_tiny_cohort_round_enqueue")
-        torch.cuda.synchronize()
-        return self
-
-    def state(self):
-        out = [self.glob, self.cparams, self.cmom, self.loss] + self.keep
-        return [t.clone() for t in out + ([self.wprep] if self.wprep is not None else [])]
+def Cohort(*args, prox_mu=0.0, with_prox_field=True, **kw):
+    """The harness's round with ``prox_mu`` named, unless ``with_prox_field`` is False."""
+    return cohort_harness.Cohort(*args, prox_mu=prox_mu if with_prox_field else None, **kw)
 
 
 def _data(L, nc, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(N, L, generator=g).cuda()
-    y32 = torch.randint(0, nc, (N,), generator=g).to(torch.int32).cuda()
-    return x, y32
-
-
-def _flat(nc, seed=1):
-    torch.manual_seed(seed)
-    return torch.cat([p.detach().reshape(-1) for p in TinyECG(num_classes=nc).parameters()]).cuda()
-
-
-def _table(S, rows, seed=2):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(0, N, (S, rows), generator=g).to(torch.int32).cuda()
+    return cohort_harness._data(L, nc, seed)[1:]
 
 
 @pytest.mark.parametrize("precision", ["bf16", "fp32"])
