@@ -191,10 +191,13 @@ __device__ __forceinline__ s16x4 lds_tr16(const __bf16* p) {
 //   conv2 dgrad dh1^T[ci][t] = (g W2)[ci][(k,co)] x m[(k,co)][t], times relu'(h1), written over h1
 //   conv1 wgrad dW1ext[ci][kk] = dh1^T[ci][t] x xcol[t][kk]   (both operands by transposing reads; kk = 7 -> db1)
 // The fp32 path keeps conv1 / conv1-wgrad on VALU (exact f32) and the time-major MFMA orientation.
-template <int WAVES, bool F32, bool PF = false, bool PK = false>
+// LEAN (the MODE 4 kernels only): the same values by fewer vector instructions - conv1_operand_packed, the head wave's
+// g broadcast and row_store; every other instantiation keeps its code (profiles/r19/step_isa_account.txt).
+template <int WAVES, bool F32, bool PF = false, bool PK = false, bool LEAN = false>
 struct TinySample {
   static_assert(!(PF && F32), "prepared fragments are bf16 operands");
   static_assert(!PK || PF, "packed window rows feed the prepared-fragment kernel only");
+  static_assert(!LEAN || PK, "the lean forms are written for the packed-row kernel");
   using AT = std::conditional_t<F32, float, __bf16>;  // activation / MFMA operand type
   static constexpr int NT = WAVES * 64;
   Smem sm;
@@ -343,10 +346,20 @@ struct TinySample {
   // permute puts the window's last element under the flag.  An out-of-range load is all zero and has no flag.
   __device__ __forceinline__ bf16x8 conv1_operand_packed(u32x4 d, int t) const {
     static_assert(kPackLead % 2 == 0, "the shift below assumes an even lead: window start t + kPackLead - 3");
-    const bool odd = !(lane & 1);  // t even: t + kPackLead - 3 is odd, the window starts at element 1
-    const unsigned sh = odd ? 16u : 0u;
     const unsigned flag = (h == 0 && t < L) ? 0x3f80u : 0u;  // bf16 1.0
     u32x4 o;
+    if constexpr (LEAN) {
+      // The shift count and the permute selector as lane-constant registers, computed by arithmetic: written as
+      // selects (below), hipcc turns every funnel shift into a byte permute plus a select on the parity - two
+      // instructions per dword where one v_alignbit_b32 with its count in a register does it.
+      const unsigned sh = ((lane & 1u) ^ 1u) << 4;  // 16: t even, the window starts at element 1 of the load
+#pragma unroll
+      for (int i = 0; i < 3; ++i) o[i] = __builtin_amdgcn_alignbit(d[i + 1], d[i], sh);
+      o[3] = __builtin_amdgcn_perm(flag, d[3], 0x05040100u + (sh >> 3) * 0x0101u);  // 0x05040302 when sh = 16
+      return __builtin_bit_cast(bf16x8, o);
+    }
+    const bool odd = !(lane & 1);  // t even: t + kPackLead - 3 is odd, the window starts at element 1
+    const unsigned sh = odd ? 16u : 0u;
 #pragma unroll
     for (int i = 0; i < 3; ++i) o[i] = __builtin_amdgcn_alignbit(d[i + 1], d[i], sh);
     // bytes {flag.b1, flag.b0, d3 high or low half}
@@ -690,10 +703,23 @@ struct TinySample {
           // phase 4 needs no barrier of its own.  B[r][ci] = g[co] * w2[co][ci][k], co = 8(h&1) + j: the same
           // products and rounding as the per-wave scaling of the LDS-built kernel (bitwise equal operands).
           float gq[8];
+          if constexpr (LEAN) {
+            // Every 16-lane row of this wave holds g[0 .. 15] in lane order (each quarter computes all 16 channels
+            // from the same broadcasts), so gq[j] = g[8(h&1) + j] is a move inside the row: odd quarters rotate
+            // their row by 8 lanes, then lane j of each row is broadcast over the row - 10 DPP moves and selects
+            // instead of 16 v_readlane, 16 moves out of the SGPRs and 8 selects.
+            const int gi = __builtin_bit_cast(int, gl);
+            const int gr = (h & 1) ? __builtin_amdgcn_update_dpp(0, gi, 0x128, 0xf, 0xf, false) : gi;  // row_ror:8
+#define ECG_ROW_BCAST(j) gq[j] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, gr, 0x150 + (j), 0xf, 0xf, false));
+            ECG_ROW_BCAST(0) ECG_ROW_BCAST(1) ECG_ROW_BCAST(2) ECG_ROW_BCAST(3)
+            ECG_ROW_BCAST(4) ECG_ROW_BCAST(5) ECG_ROW_BCAST(6) ECG_ROW_BCAST(7)  // row_newbcast:j
+#undef ECG_ROW_BCAST
+          } else {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float lo = lane_bcast(gl, j), hi = lane_bcast(gl, 8 + j);
-            gq[j] = (h & 1) ? hi : lo;
+            for (int j = 0; j < 8; ++j) {
+              const float lo = lane_bcast(gl, j), hi = lane_bcast(gl, 8 + j);
+              gq[j] = (h & 1) ? hi : lo;
+            }
           }
 #pragma unroll
           for (int s = 0; s < 3; ++s) {
@@ -941,6 +967,36 @@ struct TinySample {
   __device__ __forceinline__ void row_store(__amdgpu_buffer_rsrc_t r, int rowbase) const {
     constexpr int NQ = C * C * K2 / 4;  // 320 quads of conv2 weights
     static_assert(NQ + 128 + C <= NT || WAVES < 16, "one job per thread at 16 waves");
+    if constexpr (LEAN) {
+      // The three thread ranges are whole waves (320 = 5 x 64, 448 = 7 x 64): scalar branches on the wave index, and
+      // each range reads its own partials directly - row_value's sums in row_value's order, without its chain of
+      // range tests and without the division by K1 (the conv1 range takes the partials' own [ci][8] order).
+      static_assert(NQ % 64 == 0 && (NQ + 128) % 64 == 0, "thread ranges are whole waves");
+      if (w >= NQ / 64) {
+        if (w < (NQ + 128) / 64) {
+          const int j = tid - NQ, ci = j >> 3, kk = j & 7;  // kk < 7: dW1[ci][kk]; kk = 7: db1[ci]
+          float v = 0.f;
+#pragma unroll
+          for (int ww = 0; ww < WAVES; ++ww) v += red[red_dw1(WAVES) + ww * 128 + j];
+          st_wt(r, rowbase + (kk < K1 ? lay.w1 + ci * K1 + kk : lay.b1 + ci), v);
+        } else {
+          const int co = tid - NQ - 128, i = lay.b2 + co;  // conv2 bias, then head and loss
+          if (i <= lay.P) {
+            float v;
+            if (i >= lay.wh) {
+              v = red[red_head(WAVES) + (i - lay.wh)];
+            } else {
+              v = 0.f;
+#pragma unroll
+              for (int pp = 0; pp < msplit(WAVES); ++pp) v += red[red_cnt(WAVES) + pp * 16 + co];
+              v *= red[RED_G + co];
+            }
+            st_wt(r, rowbase + i, v);
+          }
+        }
+        return;
+      }
+    }
     if (tid < NQ) {
       const int e0 = 4 * tid;
       f32x4 v = *reinterpret_cast<const f32x4*>(red + red_m(WAVES) + e0);
@@ -1003,7 +1059,8 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     const int* __restrict__ idx,                         // [B] rows of X for this step (nullptr: b; PK: unused)
     int slab_wt) {                                       // FusedOpt::slab_wt
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  TinySample<WAVES, F32, PF, PK> S(smem, L, nc);
+  using Sample = TinySample<WAVES, F32, PF, PK, MODE == 4>;  // LEAN: the MODE 4 kernels only
+  Sample S(smem, L, nc);
   constexpr bool TRAIN = MODE != 1;
   constexpr bool COHORT = MODE == 3;
   constexpr bool PKI = MODE == 4;
@@ -1045,7 +1102,7 @@ __global__ __launch_bounds__(WAVES * 64) void tiny_ecg_step_kernel(
     const float* xrow = X + row * pitch;
     // exactly the row (bf16); PK: the whole packed row, pads included
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t xr = make_rsrc(xrow, PK ? pitch * 4 : (long)L * 4);
-    [[maybe_unused]] typename TinySample<WAVES, F32, PF, PK>::X1 x0;
+    [[maybe_unused]] typename Sample::X1 x0;
     [[maybe_unused]] float hv_pk = 0.f;
     if constexpr (PK) {
       // Every address here is made of preloaded arguments and the workgroup / lane ids, so the loads go out in
