@@ -83,8 +83,16 @@ class FedAvgConfig:
     prox_mu: float = 0.0
     # how a GPU's training windows are dealt to its virtual clients (needs clients_per_gpu > 1): contiguous slices, or
     # "shards" - client_shards runs of the label-sorted windows per client (label-skewed, non-IID clients)
+    # "dirichlet" - the label-Dirichlet split with concentration client_alpha (> 0, no default): clients of unequal
+    # sizes and label mixes
     client_partition: str = "contiguous"
     client_shards: int = 2
+    client_alpha: float = 0.0
+    # unequal local work and the aggregate of a cohort round (need clients_per_gpu > 1): local_epochs E > 0 - a virtual
+    # client of n_k windows runs min(local_steps, max(1, E * (n_k // batch_size))) local steps (0: local_steps each);
+    # aggregate mean | weighted (n_k / n over the cohort) | nova (FedNova's normalised averaging)
+    local_epochs: int = 0
+    aggregate: str = "mean"
     results_csv: str = "results/fedavg_results.csv"
     jsonl: Optional[str] = None
     model: str = "tiny_ecg"

@@ -260,7 +260,7 @@ class DeviceIndexSampler:
         return self.fill(t)[0]
 
 
-PARTITIONS = ("contiguous", "shards")
+PARTITIONS = ("contiguous", "shards", "dirichlet")
 
 
 def shard_partition(y: torch.Tensor, clients: int, shards_per_client: int, seed: Optional[int]) -> torch.Tensor:
@@ -288,14 +288,74 @@ def shard_partition(y: torch.Tensor, clients: int, shards_per_client: int, seed:
     return order[perm].reshape(K, s * rows).to(torch.int64).contiguous()
 
 
+def dirichlet_partition(y: torch.Tensor, clients: int, alpha: float, min_rows: int,
+                        seed: Optional[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Clients of unequal sizes and label mixes, the label-Dirichlet split of Hsu et al. ("Measuring the Effects of
+    Non-Identical Data Distribution for Federated Visual Classification"): ``(order, sizes)`` on ``y``'s device, int64
+    ``[K, n_max]`` and ``[K]``; row k of ``order`` holds client k's dataset rows in its first ``sizes[k]`` entries (the
+    rest repeats its first row: valid rows that no sampler reads).
+
+    For every class in ascending order, the class's rows - in a host permutation - are dealt to the K clients in
+    proportions ``q ~ Dir(alpha)``: client k takes entries ``[floor(c_{k-1} n), floor(c_k n))`` of the n permuted rows,
+    c the running sum of q (c_K = 1).  Small alpha: most of a class goes to few clients.  Then, in ascending client
+    order, a client below ``min_rows`` (a batch) is topped up from the tail of the currently largest client (the
+    lowest id among equals), which never drops below ``min_rows`` itself.  Every row belongs to at most one client.
+    Permutations and proportions come from one host generator seeded from ``mix64(seed)``: a pure function of its
+    arguments, so a resumed run rebuilds the partition it had."""
+    from ..utils.philox import mix64
+    K, m = int(clients), int(min_rows)
+    if K < 1 or m < 1 or not alpha > 0:
+        raise ValueError(f"need clients >= 1, min_rows >= 1 and alpha > 0, got {K}, {m} and {alpha}")
+    if y.dim() != 1:
+        raise ValueError("labels must be a vector [N]")
+    if y.shape[0] < K * m:
+        raise RuntimeError(f"{y.shape[0]} windows are fewer than {K} clients x {m} rows")
+    g = torch.Generator()
+    g.manual_seed(mix64(0 if seed is None else int(seed)) & ((1 << 63) - 1))
+    yc = y.detach().cpu()
+    parts: List[List[torch.Tensor]] = [[] for _ in range(K)]
+    for c in torch.unique(yc).tolist():  # (sorted)
+        rows = torch.nonzero(yc == c).reshape(-1)
+        rows = rows[torch.randperm(rows.numel(), generator=g)]
+        q = torch._standard_gamma(torch.full((K,), float(alpha), dtype=torch.float64), generator=g)
+        if not float(q.sum()) > 0.0:  # every draw underflowed (alpha << 1): the whole class to one client
+            q = torch.zeros(K, dtype=torch.float64)
+            q[int(torch.randint(K, (1,), generator=g))] = 1.0
+        cuts = torch.floor(torch.cumsum(q / q.sum(), 0) * rows.numel()).to(torch.int64).clamp_(0, rows.numel())
+        cuts[-1] = rows.numel()
+        lo = 0
+        for k in range(K):
+            hi = max(lo, int(cuts[k]))
+            parts[k].append(rows[lo:hi])
+            lo = hi
+    own = [torch.cat(p) if p else torch.zeros(0, dtype=torch.int64) for p in parts]
+    for k in range(K):
+        while own[k].numel() < m:
+            d = max(range(K), key=lambda j: (own[j].numel(), -j))
+            t = min(m - own[k].numel(), own[d].numel() - m)
+            if d == k or t < 1:
+                raise RuntimeError(f"cannot give every one of {K} clients {m} rows")  # (unreachable: N >= K * m)
+            own[k] = torch.cat([own[k], own[d][-t:]])
+            own[d] = own[d][:-t]
+    sizes = torch.tensor([o.numel() for o in own], dtype=torch.int64)
+    order = torch.stack([torch.cat([o, o[:1].expand(int(sizes.max()) - o.numel())]) for o in own])
+    return order.contiguous().to(y.device), sizes.to(y.device)
+
+
 def client_partition(partition: str, y: torch.Tensor, clients: int, shards_per_client: int, seed: Optional[int],
-                     device) -> Optional[torch.Tensor]:
+                     device, alpha: float = 0.0, min_rows: int = 1):
     """The ``order`` argument of ``CohortSampler`` for a trainer's ``partition``: None for "contiguous" (client k owns
-    rows ``[k * n, (k + 1) * n)``), ``shard_partition`` of the labels on ``device`` for "shards"."""
-    if partition not in PARTITIONS:
-        raise ValueError(f"partition must be one of {list(PARTITIONS)}, got {partition!r}")
+    rows ``[k * n, (k + 1) * n)``), ``shard_partition`` of the labels on ``device`` for "shards".  "dirichlet":
+    ``dirichlet_partition(y, clients, alpha, min_rows, seed)`` on ``device`` - the pair ``(order, sizes)``, ``CohortSampler``'s
+    ``order`` and ``sizes``."""
+    if partition not in PARTITIONS or (partition == "dirichlet" and not alpha > 0):
+        raise ValueError(f"partition must be one of {list(PARTITIONS)}, dirichlet together with its concentration "
+                         f"alpha > 0 (there is no default); got {partition!r} with alpha {alpha:g}")
     if partition == "contiguous":
         return None
+    if partition == "dirichlet":
+        order, sizes = dirichlet_partition(y, clients, alpha, min_rows, seed)
+        return order.to(device), sizes.to(device)
     return shard_partition(y, clients, shards_per_client, seed).to(device)
 
 
@@ -314,11 +374,19 @@ class CohortSampler:
     ``order`` (int64 ``[clients, n]``, e.g. ``shard_partition``): client k's local row j is dataset row ``order[k, j]``
     instead of ``k * n + j``, and ``n`` is its row length; None: the contiguous partitions, the tables of before.
 
+    ``sizes`` (int64 ``[clients]``, with ``order``; e.g. ``dirichlet_partition``): clients of unequal sizes - client k
+    owns the first ``n_k = sizes[k]`` entries of its ``order`` row.  Its local row for position t of a round (t in
+    ``[0, steps * B)``, step ``t // B``) is entry ``t % n_k`` of its permutation number ``t // n_k``: consecutive slices of
+    fresh permutations of ITS partition, as above, with ``passes = ceil(steps * B / min(sizes))`` permutations drawn
+    per client.  Every table entry is a row of its client's own partition, the steps that ``steps_of`` cuts off
+    included (the round still reads them).  None: equal sizes, the tables of before, bit for bit.
+
     The sampler holds no state between rounds: a run resumed at round r draws what the uninterrupted run drew.
     """
 
     def __init__(self, n_windows: int, batch_size: int, steps: int, clients: int, cohort: int, device,
-                 seed: Optional[int] = None, order: Optional[torch.Tensor] = None):
+                 seed: Optional[int] = None, order: Optional[torch.Tensor] = None,
+                 sizes: Optional[torch.Tensor] = None):
         if clients < 1 or not 1 <= cohort <= clients:
             raise ValueError(f"need 1 <= cohort <= clients, got cohort {cohort} of {clients} clients")
         self.N, self.B, self.S, self.K, self.M = int(n_windows), int(batch_size), int(steps), int(clients), int(cohort)
@@ -332,10 +400,18 @@ class CohortSampler:
                 raise ValueError(f"order holds rows outside [0, {self.N})")
             self.order = order.to(self.device)
             self.n = int(order.shape[1])
-        if self.n < self.B:
-            raise RuntimeError(f"{self.N} windows over {self.K} clients leave {self.n} per client < batch {self.B}")
+        self.sizes: Optional[List[int]] = None
+        if sizes is not None:
+            if self.order is None:
+                raise ValueError("sizes need order: the rows of clients of unequal sizes")
+            self.sizes = [int(v) for v in sizes.tolist()]
+            if len(self.sizes) != self.K or min(self.sizes) < 1 or max(self.sizes) > self.n:
+                raise ValueError(f"sizes must be {self.K} values in [1, {self.n}]")
+        n_min = self.n if self.sizes is None else min(self.sizes)
+        if n_min < self.B:
+            raise RuntimeError(f"{self.N} windows over {self.K} clients leave {n_min} per client < batch {self.B}")
         self.seed = 0 if seed is None else int(seed)
-        self.passes = (self.S * self.B + self.n - 1) // self.n  # permutations of a partition per client and round
+        self.passes = (self.S * self.B + n_min - 1) // n_min  # permutations of a partition per client and round
 
     def _round_seed(self, r: int) -> int:
         from ..utils.philox import mix64
@@ -358,7 +434,17 @@ class CohortSampler:
         g.manual_seed(mix64(self._round_seed(r)))
         keys = torch.randint(0, 1 << 62, (self.M, self.passes, self.n), device=self.device, generator=g,
                              dtype=torch.int64)
-        rows = keys.argsort(dim=2).reshape(self.M, self.passes * self.n)[:, : self.S * self.B]
+        if self.sizes is not None:
+            # entries past a client's n_k get a key above every drawn one: the argsort's first n_k are a uniform
+            # permutation of its partition
+            nk = torch.tensor([self.sizes[i] for i in ids], dtype=torch.int64).to(self.device)
+            pos = torch.arange(self.n, device=self.device)
+            keys = torch.where(pos[None, None, :] < nk[:, None, None], keys, torch.full_like(keys, 1 << 62))
+            t = torch.arange(self.S * self.B, device=self.device)[None, :]
+            perm = keys.argsort(dim=2).reshape(self.M, self.passes * self.n)
+            rows = perm.gather(1, (t // nk[:, None]) * self.n + t % nk[:, None])
+        else:
+            rows = keys.argsort(dim=2).reshape(self.M, self.passes * self.n)[:, : self.S * self.B]
         if self.order is None:
             rows = rows + (torch.tensor(ids, dtype=torch.int64) * self.n).to(self.device)[:, None]
         else:
@@ -366,3 +452,17 @@ class CohortSampler:
         # [M, S, B] -> [S, M, B]: a step's row holds the clients' batches back to back
         table.copy_(rows.view(self.M, self.S, self.B).permute(1, 0, 2).reshape(self.S, self.M * self.B))
         return ids
+
+    def sizes_of(self, ids: List[int]) -> List[int]:
+        """The partition sizes n_k of the clients ``ids``."""
+        return [self.n if self.sizes is None else self.sizes[i] for i in ids]
+
+    def steps_of(self, ids: List[int], local_epochs: int) -> List[int]:
+        """Local steps of the clients ``ids`` for ``local_epochs`` E passes over their own rows in batches of B:
+        ``S_k = min(S, max(1, E * (n_k // B)))``; E == 0: S for everyone."""
+        E = int(local_epochs)
+        if E < 0:
+            raise ValueError("local_epochs must be >= 0")
+        if E == 0:
+            return [self.S] * len(ids)
+        return [min(self.S, max(1, E * (n // self.B))) for n in self.sizes_of(ids)]

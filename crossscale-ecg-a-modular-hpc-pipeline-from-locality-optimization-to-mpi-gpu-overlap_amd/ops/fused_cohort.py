@@ -7,8 +7,7 @@ The fused step kernel runs one workgroup per window, so a client with a small ba
 cohort's ``cohort * B`` windows and ONE reduce + SGD launch over its clients, then the clients' mean in ascending
 cohort order into the global weights - captured into one hipGraph like a single client's round.  Virtual clients keep
 no state between rounds (weights from the global model, zero momentum), and which clients and rows a round uses is a
-pure function of ``(seed, round)`` (``data.dataset.CohortSampler``).  Limits: no DP-SGD in a cohort, equal client
-sizes, plain (unweighted) mean.
+pure function of ``(seed, round)`` (``data.dataset.CohortSampler``).  Limit: no DP-SGD in a cohort.
 
 Client-level DP (``client_dp_clip`` > 0; DP-FedAvg) and a server step size ``server_lr`` != 1 close the round with
 ``cohort_delta_scale_kernel`` + ``cohort_dp_mean_kernel`` in place of the mean: every client's round delta clipped to
@@ -34,6 +33,15 @@ leaves g there and no launch writes it before the close, so the round needs no c
 
 ``partition="shards"`` deals the clients label-skewed partitions (``data.dataset.shard_partition``: ``shards_per_client``
 runs of the label-sorted windows each) instead of contiguous slices of the windows.
+
+Unequal clients: ``partition="dirichlet"`` (``data.dataset.dirichlet_partition`` with ``dirichlet_alpha``: clients of
+unequal sizes n_k and label mixes), ``local_epochs`` E > 0 (client c runs ``S_c = min(S, max(1, E * (n_c // B)))`` of the
+round's S steps and is frozen for the rest: the STEPS form of the cohort reduce, ``slab_reduce_cohort_steps_*``) and
+``aggregate`` "weighted" (n_c / n, FedAvg's own weights) or "nova" (FedNova) in place of "mean": the close is then
+``cohort_delta_wscale_kernel`` + the second kernel of whichever close the round has, on the weights of
+``train.cohort.weights_of``.  Step counts and weights change with every round's cohort, so they live in device arrays
+the kernels read - one pair per index table, filled by ``stage()`` beside it - and one captured graph serves every
+round.  A weighted close takes no clip and no noise.
 """
 from __future__ import annotations
 
@@ -48,7 +56,8 @@ from ..data.dataset import CohortSampler, client_partition
 from ..models.tiny_ecg import TinyECG, num_params
 from .fused_tiny import _check_dataset, labels_int32, prec_id, slab_stride
 from .tiny_eval import EvalResult, TinyEvaluator, tiny_evaluate
-from ..train.cohort import check_client_dp, client_dp_seed_of, client_dp_sigma_share, load_server_state
+from ..train.cohort import (check_aggregate, check_client_dp, client_dp_seed_of, client_dp_sigma_share,
+                            cohort_round_shape, load_server_state)
 from ..train.server_opt import BETA1, BETA2, TAU, check_server_opt, check_server_scope, server_opt_init
 
 
@@ -63,9 +72,11 @@ class FusedCohortTrainer:
                  client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
                  server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
                  server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank",
-                 prox_mu: float = 0.0, partition: str = "contiguous", shards_per_client: int = 2):
+                 prox_mu: float = 0.0, partition: str = "contiguous", shards_per_client: int = 2,
+                 dirichlet_alpha: float = 0.0, local_epochs: int = 0, aggregate: str = "mean"):
         if not prox_mu >= 0.0:
             raise ValueError(f"prox_mu must be >= 0, got {prox_mu}")
+        check_aggregate(aggregate, local_epochs, nesterov, prox_mu, client_dp_clip)
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients: the cohort "
                              "reduce has no per-sample clip")
@@ -89,9 +100,13 @@ class FusedCohortTrainer:
         self.M = self.K if not cohort else int(cohort)
         self.lr, self.momentum, self.wd, self.nesterov = float(lr), float(momentum), float(weight_decay), bool(nesterov)
         self.partition, self.shards_per_client = partition, int(shards_per_client)
-        order = client_partition(partition, y_gpu, self.K, self.shards_per_client, seed, self.device)
+        self.dirichlet_alpha, self.local_epochs, self.aggregate = float(dirichlet_alpha), int(local_epochs), aggregate
+        self.hetero = partition == "dirichlet" or self.local_epochs > 0 or aggregate != "mean"
+        order = client_partition(partition, y_gpu, self.K, self.shards_per_client, seed, self.device,
+                                 alpha=self.dirichlet_alpha, min_rows=self.B)
+        order, sizes = order if isinstance(order, tuple) else (order, None)
         self.sampler = CohortSampler(self.x.shape[0], self.B, self.S, self.K, self.M, self.device, seed=seed,
-                                     order=order)
+                                     order=order, sizes=sizes)
         self.prox_mu = float(prox_mu)
         lib = _lib.kernels()
         L = self.x.shape[1]
@@ -121,7 +136,17 @@ class FusedCohortTrainer:
         self.round_clients: List[int] = []  # the cohort of the last round taken
         self.cohort_round = 0  # rounds taken so far = the round the next staging draws
         self._loss_steps = 0
+        self._loss_samples = 0  # B * sum_c S_c of the rounds since the loss words were reset
         self.steps_done = 0
+        # unequal clients: one (step counts, weights) pair per index table - stage() fills the pair of idx_stage while
+        # the round before may still read the other - holding values every graph can run on until then
+        self._pairs: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._shape: Tuple[List[int], List[int], List[float]] = ([], [], [])
+        self._staged_shape = self._shape
+        if self.hetero:
+            for t in (self.idx_table, self.idx_stage):
+                self._pairs[t.data_ptr()] = (torch.full((self.M,), self.S, dtype=torch.int32, device=self.device),
+                                             torch.full((self.M,), 1.0 / self.M, **f32))
         self.use_graph = (os.environ.get("ECG_TINY_GRAPH", "1") != "0") if use_graph is None else bool(use_graph)
         self._graphs = {}
         self._evaluator: Optional[TinyEvaluator] = None
@@ -136,7 +161,8 @@ class FusedCohortTrainer:
         # address) and always takes the two-launch close, so the factor, norm and round-word buffers always exist
         split = self.server_scope == "global"
         self.server_delta = torch.zeros(self.P, **f32) if split else None
-        self.client_dp = self.cdp_clip > 0.0 or self.server_lr != 1.0 or server_opt != "none" or split
+        self.client_dp = (self.cdp_clip > 0.0 or self.server_lr != 1.0 or server_opt != "none" or split
+                          or aggregate != "mean")
         self.cdp_scale = self.cdp_norm = self.cdp_round = None
         if self.client_dp:
             self.cdp_scale = torch.ones(self.M, **f32)
@@ -165,6 +191,10 @@ class FusedCohortTrainer:
     def _round_of(self, n: int, table: torch.Tensor):
         r = self._round
         r.idx, r.steps = table.data_ptr(), n
+        if self.hetero:  # the table's own pair; the weights only where the close is a weighted one
+            st, w = self._pairs[table.data_ptr()]
+            r.client_steps = st.data_ptr()
+            r.client_weight = w.data_ptr() if self.aggregate != "mean" else None
         return C.byref(r)
 
     def _graph_for(self, n: int, table: torch.Tensor) -> C.c_void_p:
@@ -202,6 +232,7 @@ class FusedCohortTrainer:
         lib = _lib.kernels()
         sizes = [self._check_n(n) for n in sizes]
         state = (self.params, self.loss_acc, self.idx_stage, self.idx_table)
+        state += tuple(t for pair in self._pairs.values() for t in pair)
         if self.client_dp:
             state += (self.cdp_round, self.cdp_scale, self.cdp_norm)
         state += tuple(t for t in (self.server_m, self.server_v) if t is not None)
@@ -253,6 +284,12 @@ class FusedCohortTrainer:
         the first ``n_steps`` rows of the table the sampler draws for a full round)."""
         n = self._check_n(n_steps)
         self._staged_clients = self.sampler.fill(self.cohort_round, self.idx_stage)
+        self._staged_shape = cohort_round_shape(self.sampler, self._staged_clients, n, self.local_epochs,
+                                                self.aggregate, self.momentum)
+        if self.hetero:  # 1 <= steps <= n: the native round cannot check device values
+            st, w = self._pairs[self.idx_stage.data_ptr()]
+            st.copy_(torch.tensor(self._staged_shape[1], dtype=torch.int32), non_blocking=True)
+            w.copy_(torch.tensor(self._staged_shape[2], dtype=torch.float32), non_blocking=True)
         self._staged = n
 
     def prepare_round(self, n_steps: Optional[int] = None, reset_loss: bool = True) -> None:
@@ -260,6 +297,7 @@ class FusedCohortTrainer:
         if reset_loss:
             self.loss_acc.zero_()
             self._loss_steps = 0
+            self._loss_samples = 0
         if self._staged != n:
             if self._staged is not None:
                 raise RuntimeError(f"{self._staged} rows are staged for the next round, not {n}")
@@ -272,9 +310,11 @@ class FusedCohortTrainer:
         self._staged = None
         self.idx_table, self.idx_stage = self.idx_stage, self.idx_table
         self.round_clients = self._staged_clients
+        self._shape = self._staged_shape
         self.cohort_round += 1
         self.steps_done += n
         self._loss_steps += n
+        self._loss_samples += self.B * (sum(self._shape[1]) if self.hetero else self.M * n)
         return self.idx_table
 
     def run_round(self, n_steps: Optional[int] = None, reset_loss: bool = True, next_n: Optional[int] = None) -> None:
@@ -325,5 +365,10 @@ class FusedCohortTrainer:
         return self._evaluator.run(self.params, x, y32)
 
     def avg_loss(self) -> float:
-        """Mean per-sample loss over the cohort's clients and the steps since the last reset (synchronises)."""
-        return float(self.loss_acc.sum().item()) / (self.M * self.B * max(1, self._loss_steps))
+        """Mean per-sample loss over the cohort's clients and the steps they ran since the last reset - ``B * sum_c
+        S_c`` samples per round (synchronises)."""
+        return float(self.loss_acc.sum().item()) / max(1, self._loss_samples)
+
+    def last_round_shape(self) -> Tuple[List[int], List[int], List[float]]:
+        """The last round's cohort: its clients' sizes, local steps and aggregation weights, in cohort order."""
+        return self._shape

@@ -29,6 +29,16 @@ FedProx (``prox_mu`` mu > 0): every client's local objective gains ``mu / 2 * |w
 round started from: after ``backward()`` every ``p.grad`` gains ``mu * (p - g)`` in fp32, before ``opt.step()`` - the
 definition ``slab_reduce_cohort_prox_sgd_kernel`` implements.  ``partition="shards"``: label-skewed clients
 (``data.dataset.shard_partition``).
+
+Unequal clients (``partition="dirichlet"`` with ``dirichlet_alpha``: ``data.dataset.dirichlet_partition``, client k owns
+``n_k`` rows), unequal local work (``local_epochs`` E > 0: client c of the cohort runs the first
+``S_c = min(S, max(1, E * (n_c // B)))`` rows of its table columns; 0: all S) and the aggregate (``weights_of``):
+``Delta = ((w_0 d_0 + w_1 d_1) + ...) + w_{M-1} d_{M-1}`` in ascending cohort order in fp32, with ``p_c = n_c / sum n_c``
+over the cohort and w_c = ``p_c`` ("weighted", FedAvg's own weights) or ``p_c * tau_eff / a_c`` ("nova", FedNova: Wang et
+al., "Tackling the Objective Inconsistency Problem in Heterogeneous Federated Optimization"); "mean" keeps the closes
+above, ``1 / M`` each.  Delta then takes the server step or the split close exactly as the unweighted one does; there is
+no clip and no noise on a weighted Delta (its sensitivity is not C / M).  ``cohort_delta_wscale_kernel`` and the STEPS
+form of the cohort reduce implement these definitions.  Every rank normalises over its own cohort.
 """
 from __future__ import annotations
 
@@ -55,8 +65,10 @@ class TorchCohortTrainer:
                  client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
                  server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
                  server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank",
-                 prox_mu: float = 0.0, partition: str = "contiguous", shards_per_client: int = 2):
+                 prox_mu: float = 0.0, partition: str = "contiguous", shards_per_client: int = 2,
+                 dirichlet_alpha: float = 0.0, local_epochs: int = 0, aggregate: str = "mean"):
         check_prox(prox_mu, amp_dtype, model)
+        check_aggregate(aggregate, local_epochs, nesterov, prox_mu, client_dp_clip)
         self.prox_mu = float(prox_mu)
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients")
@@ -70,8 +82,16 @@ class TorchCohortTrainer:
         self.opt_args = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
         self.amp_dtype = amp_dtype
         self.partition, self.shards_per_client = partition, int(shards_per_client)
-        order = client_partition(partition, y, self.K, self.shards_per_client, seed, self.device)
-        self.sampler = CohortSampler(x.shape[0], self.B, self.S, self.K, self.M, self.device, seed=seed, order=order)
+        self.dirichlet_alpha, self.local_epochs, self.aggregate = float(dirichlet_alpha), int(local_epochs), aggregate
+        self.momentum = float(momentum)
+        self.hetero = partition == "dirichlet" or self.local_epochs > 0 or aggregate != "mean"
+        order = client_partition(partition, y, self.K, self.shards_per_client, seed, self.device,
+                                 alpha=self.dirichlet_alpha, min_rows=self.B)
+        order, sizes = order if isinstance(order, tuple) else (order, None)
+        self.sampler = CohortSampler(x.shape[0], self.B, self.S, self.K, self.M, self.device, seed=seed, order=order,
+                                     sizes=sizes)
+        self._shape: Tuple[List[int], List[int], List[float]] = ([], [], [])
+        self._loss_client_steps = 0
         self.table = torch.zeros((self.S, self.M * self.B), dtype=torch.int32, device=self.device)
         self.work = copy.deepcopy(model)  # one client's model: reloaded from the global weights per client
         if getattr(self.work, "_flat", None) is not None:
@@ -129,15 +149,28 @@ class TorchCohortTrainer:
             self.loss_acc += loss.detach().float()
         return [p.detach().clone() for p in self.work.parameters()]
 
-    def run_table(self, n: int, table: torch.Tensor, r: Optional[int] = None) -> None:
+    def round_shape(self, ids: List[int], n: int) -> Tuple[List[int], List[int], List[float]]:
+        """(sizes, steps, weights) of the cohort ``ids`` in a round of ``n`` steps: ``n_c``, ``min(n, S_c)`` and
+        ``weights_of`` of the two."""
+        return cohort_round_shape(self.sampler, ids, n, self.local_epochs, self.aggregate, self.momentum)
+
+    def last_round_shape(self) -> Tuple[List[int], List[int], List[float]]:
+        """The last round's cohort: its clients' sizes, local steps and aggregation weights, in cohort order."""
+        return self._shape
+
+    def run_table(self, n: int, table: torch.Tensor, r: Optional[int] = None,
+                  steps: Optional[List[int]] = None, weights: Optional[List[float]] = None) -> None:
         """One cohort round on ``table`` (int32 ``[>= n, M * B]``): the clients one after another, then the mean (or
-        the DP close, which draws the noise of round ``r``; default: the round counter)."""
-        if self.client_dp:
-            self._run_table_client_dp(n, table, self.cohort_round if r is None else r)
+        the DP close, which draws the noise of round ``r``; default: the round counter).  ``steps`` [M]: client j runs
+        its first ``steps[j]`` table rows (default: n each); ``weights`` [M] (fp32 values): the weighted close."""
+        steps = [n] * self.M if steps is None else [min(n, int(v)) for v in steps]
+        self._steps = steps
+        if self.client_dp or weights is not None:
+            self._run_table_client_dp(n, table, self.cohort_round if r is None else r, weights)
         else:
             total = None
             for j in range(self.M):
-                ps = self._client_round(j, n, table)
+                ps = self._client_round(j, steps[j], table)
                 total = ps if total is None else [t + p for t, p in zip(total, ps)]
             inv = torch.tensor(1.0 / self.M, dtype=torch.float32, device=self.device)  # fp32(1 / M), rounded once
             with torch.no_grad():
@@ -145,22 +178,26 @@ class TorchCohortTrainer:
                     pg.copy_(t * inv)
         self.steps_done += n
         self._loss_steps += n
+        self._loss_client_steps += sum(steps)
 
-    def _run_table_client_dp(self, n: int, table: torch.Tensor, r: int) -> None:
-        """The DP close of round ``r`` (the module docstring's definition), everything in fp32."""
+    def _run_table_client_dp(self, n: int, table: torch.Tensor, r: int, weights: Optional[List[float]] = None) -> None:
+        """The DP close of round ``r`` (the module docstring's definition), everything in fp32.  ``weights``: the
+        weighted close - ``s_c w_c`` in place of ``s_c`` and no ``1 / M``."""
         f32 = dict(dtype=torch.float32, device=self.device)
         g = torch.cat([p.detach().reshape(-1) for p in self.model.parameters()]).float()
         acc, self._norms, self._scales = None, [], []
         for j in range(self.M):
-            d = torch.cat([p.reshape(-1) for p in self._client_round(j, n, table)]).float() - g
+            d = torch.cat([p.reshape(-1) for p in self._client_round(j, self._steps[j], table)]).float() - g
             nrm = torch.linalg.vector_norm(d)
             sc = torch.ones((), **f32)
             if self.cdp_clip > 0.0 and float(nrm) > 0.0:
                 sc = torch.minimum(sc, torch.tensor(self.cdp_clip, **f32) / nrm)
             self._norms.append(float(nrm))
             self._scales.append(float(sc))
+            if weights is not None:
+                sc = sc * torch.tensor(weights[j], **f32)
             acc = sc * d if acc is None else acc + sc * d
-        upd = acc * torch.tensor(1.0 / self.M, **f32)
+        upd = acc * torch.tensor(1.0 if weights is not None else 1.0 / self.M, **f32)
         if self.cdp_nu != 0.0:
             z = philox.normal(self.cdp_seed, r, g.numel(), stream=1).astype(np.float32)
             upd = upd + torch.tensor(self.cdp_nu, **f32) * torch.from_numpy(z).to(self.device)
@@ -207,14 +244,21 @@ class TorchCohortTrainer:
         if reset_loss:
             self.loss_acc.zero_()
             self._loss_steps = 0
+            self._loss_client_steps = 0
 
     def launch_round(self, n: int, next_n=None) -> None:
         self.round_clients = self.sampler.fill(self.cohort_round, self.table)
         self.cohort_round += 1
-        self.run_table(n, self.table, self.cohort_round - 1)
+        self._shape = self.round_shape(self.round_clients, n)
+        if self.hetero:
+            self.run_table(n, self.table, self.cohort_round - 1, self._shape[1],
+                           self._shape[2] if self.aggregate != "mean" else None)
+        else:
+            self.run_table(n, self.table, self.cohort_round - 1)
 
     def avg_loss(self) -> float:
-        return float(self.loss_acc.item()) / (self.M * max(1, self._loss_steps))
+        """Mean per-sample loss over the clients' steps since the last reset (``sum_c S_c`` per round)."""
+        return float(self.loss_acc.item()) / max(1, self._loss_client_steps)
 
 
 def load_server_state(trainer, st: Dict[str, torch.Tensor]) -> None:
@@ -226,6 +270,64 @@ def load_server_state(trainer, st: Dict[str, torch.Tensor]) -> None:
         if st[key].shape != t.shape:
             raise ValueError(f"{key} shape {tuple(st[key].shape)} != {tuple(t.shape)}")
         t.copy_(st[key].to(t.device))
+
+
+AGGREGATES = ("mean", "weighted", "nova")
+
+
+def check_aggregate(aggregate: str, local_epochs: int, nesterov: bool, prox_mu: float, client_dp_clip: float) -> None:
+    if aggregate not in AGGREGATES:
+        raise ValueError(f"aggregate must be one of {list(AGGREGATES)}, got {aggregate!r}")
+    if int(local_epochs) < 0:
+        raise ValueError("local_epochs must be >= 0")
+    if aggregate != "mean" and client_dp_clip > 0.0:
+        raise ValueError(f"aggregate {aggregate!r} is not combined with client-level DP (client_dp_clip > 0): the "
+                         "sensitivity of a weighted, clipped mean is not C / M, and no accountant here covers it")
+    if aggregate == "nova" and (nesterov or prox_mu > 0.0):
+        raise ValueError('aggregate "nova" is not combined with nesterov momentum or FedProx (prox_mu > 0): its '
+                         "normaliser a_c is derived for heavy-ball momentum SGD only")
+
+
+def nova_norm(tau: int, rho: float) -> float:
+    """a(tau, rho): the displacement of ``tau`` SGD steps under a constant unit gradient and unit learning rate with
+    heavy-ball momentum rho (m_t = rho m_{t-1} + 1, x -= m_t): ``sum_{t=1..tau} (1 - rho^t) / (1 - rho)
+    = [tau - rho (1 - rho^tau) / (1 - rho)] / (1 - rho)``; tau at rho == 0.  In double."""
+    tau, rho = int(tau), float(rho)
+    if rho == 0.0:
+        return float(tau)
+    return (tau - rho * (1.0 - rho ** tau) / (1.0 - rho)) / (1.0 - rho)
+
+
+def weights_of(sizes: List[int], steps: List[int], mode: str, momentum: float = 0.0) -> List[float]:
+    """The aggregation weights w_c of a cohort whose clients own ``sizes`` n_c rows and run ``steps`` S_c local steps
+    (both in cohort order), computed in double and rounded once to fp32 (returned as Python floats that are fp32
+    values).  With ``p_c = n_c / sum n_c``: "mean" ``1 / M``; "weighted" ``p_c``; "nova" ``p_c * tau_eff / a_c`` with
+    ``a_c = nova_norm(S_c, momentum)`` and ``tau_eff = sum_c p_c a_c`` (FedNova: every client's delta normalised by its
+    own amount of local work, the sum rescaled to the cohort's mean amount; equal steps: "weighted")."""
+    if mode not in AGGREGATES:
+        raise ValueError(f"aggregate must be one of {list(AGGREGATES)}, got {mode!r}")
+    M = len(sizes)
+    if M < 1 or len(steps) != M or min(sizes) < 1 or min(steps) < 1:
+        raise ValueError("need one size >= 1 and one step count >= 1 per client")
+    if mode == "mean":
+        w = [1.0 / M] * M
+    else:
+        total = float(sum(sizes))
+        w = [n / total for n in sizes]
+        if mode == "nova":
+            a = [nova_norm(t, momentum) for t in steps]
+            tau_eff = sum(p * ac for p, ac in zip(w, a))
+            w = [p * tau_eff / ac for p, ac in zip(w, a)]
+    return [float(np.float32(v)) for v in w]
+
+
+def cohort_round_shape(sampler, ids: List[int], n: int, local_epochs: int, aggregate: str,
+                       momentum: float) -> Tuple[List[int], List[int], List[float]]:
+    """(sizes, steps, weights) of the cohort ``ids`` in a round of ``n`` <= S steps: ``sampler.sizes_of``,
+    ``min(n, sampler.steps_of)`` and ``weights_of`` of the two - what both cohort trainers run a round with."""
+    sizes = sampler.sizes_of(ids)
+    steps = [min(int(n), s) for s in sampler.steps_of(ids, local_epochs)]
+    return sizes, steps, weights_of(sizes, steps, aggregate, momentum)
 
 
 def check_client_dp(clip: float, noise: float, server_lr: float, world_size: int) -> None:

@@ -77,6 +77,18 @@ MI355X execution (vs the reference's host-staged per-tensor MPI calls and per-st
     every GPU's training windows are sorted by label, cut into K * s shards and dealt s to a virtual client
     (``data.dataset.shard_partition``, a function of the labels, K, s and ``seed + 7919 * rank``): label-skewed clients.
     A ``prox`` event in ``--jsonl`` records mu, the partition and s; no CSV and no checkpoint changes.
+  * ``--client-partition dirichlet --client-alpha a`` / ``--local-epochs E`` / ``--aggregate {mean,weighted,nova}`` (need
+    ``--clients-per-gpu``): unequal virtual clients.  ``dirichlet`` deals every GPU's training windows by the
+    label-Dirichlet split (``data.dataset.dirichlet_partition``: sizes n_k and label mixes vary, every client holds at
+    least a batch); ``--local-epochs E`` > 0 gives client k ``min(local_steps, max(1, E * (n_k // B)))`` local steps - the
+    fused round freezes a finished client in the reduce kernel, the launches stay those of a full round;
+    ``--aggregate weighted`` averages the clients' deltas with ``n_k / n`` over the cohort, ``nova`` with FedNova's
+    ``p_k tau_eff / a_k`` (``train.cohort.weights_of``).  They compose with ``--prox-mu`` (not ``nova``), the server
+    optimizers and ``--server-scope global`` and are rejected with ``--client-dp-clip``.  ``samples_per_s`` counts the
+    ``B * sum_k S_k`` windows the cohort trained on; a ``cohort_shape`` event per round in ``--jsonl`` records rank 0's
+    sizes, steps and weights; no CSV and no checkpoint changes (all three are functions of (seed, round)).  Every rank
+    normalises over its own cohort, so under ``--sync fedavg`` the all-reduce(AVG) gives every rank's cohort the same
+    total weight, whatever its share of the windows.
 """
 from __future__ import annotations
 
@@ -216,8 +228,10 @@ def check_prox_config(cfg: FedAvgConfig, config_name: str, backend: str) -> None
     from ..data.dataset import PARTITIONS
     if not cfg.prox_mu >= 0:
         raise ValueError("--prox-mu must be >= 0")
-    if cfg.client_partition not in PARTITIONS:
-        raise ValueError(f"--client-partition must be one of {list(PARTITIONS)}, got {cfg.client_partition!r}")
+    if cfg.client_partition not in PARTITIONS or (cfg.client_partition == "dirichlet" and not cfg.client_alpha > 0):
+        raise ValueError(f"--client-partition must be one of {list(PARTITIONS)}, dirichlet together with its "
+                         f"concentration --client-alpha a > 0 (there is no default); got {cfg.client_partition!r} with "
+                         f"--client-alpha {cfg.client_alpha:g}")
     if cfg.client_shards < 1:
         raise ValueError("--client-shards must be >= 1")
     if (cfg.client_partition != "contiguous" or cfg.client_shards != 2) and cfg.clients_per_gpu <= 1:
@@ -240,6 +254,42 @@ def check_prox_config(cfg: FedAvgConfig, config_name: str, backend: str) -> None
     if cfg.overlap == "delayed":
         raise ValueError("FedProx (--prox-mu) does not support --overlap delayed: a round there starts before the "
                          "averaged model exists, so its starting weights are not the anchor FedProx defines")
+
+
+def hetero_on(cfg: FedAvgConfig) -> bool:
+    """Unequal virtual clients: a Dirichlet partition, per-client local steps or a weighted aggregate."""
+    return cfg.client_partition == "dirichlet" or cfg.local_epochs != 0 or cfg.aggregate != "mean"
+
+
+def check_hetero_config(cfg: FedAvgConfig) -> None:
+    """``--client-alpha`` / ``--local-epochs`` / ``--aggregate`` act on a cohort round's virtual clients: they need client
+    sampling, and none of them goes with client-level DP."""
+    from .cohort import AGGREGATES
+    if cfg.aggregate not in AGGREGATES:
+        raise ValueError(f"--aggregate must be one of {list(AGGREGATES)}, got {cfg.aggregate!r}")
+    if cfg.local_epochs < 0:
+        raise ValueError("--local-epochs must be >= 0")
+    if cfg.client_alpha < 0:
+        raise ValueError("--client-alpha must be > 0")
+    if cfg.client_alpha > 0 and cfg.client_partition != "dirichlet":
+        raise ValueError("--client-alpha is the concentration of --client-partition dirichlet: it needs that partition")
+    if not hetero_on(cfg):
+        return
+    if cfg.clients_per_gpu <= 1:
+        raise ValueError("--client-partition dirichlet / --local-epochs / --aggregate need client sampling "
+                         "(--clients-per-gpu K > 1): they size, time and weight a GPU's virtual clients")
+    if cfg.client_dp_clip > 0:
+        if cfg.aggregate != "mean":
+            raise ValueError(f"--aggregate {cfg.aggregate} does not support --client-dp-clip: the sensitivity of a "
+                             "weighted, clipped mean is not C / M, and no accountant here covers it")
+        if cfg.local_epochs != 0:
+            raise ValueError("--local-epochs does not support --client-dp-clip: the accountant assumes clients that "
+                             "differ in their data only, and the clip norm would bind short and long clients unevenly")
+        raise ValueError("--client-partition dirichlet does not support --client-dp-clip: the accountant's sample rate "
+                         "M / K assumes exchangeable clients, and clients of unequal sizes are not")
+    if cfg.aggregate == "nova" and cfg.prox_mu > 0:
+        raise ValueError("--aggregate nova does not support --prox-mu: its normaliser is derived for heavy-ball "
+                         "momentum SGD, not for proximal steps")
 
 
 def cohort_size(cfg: FedAvgConfig) -> int:
@@ -331,8 +381,10 @@ def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistCont
     check_client_dp_config(cfg)
     check_server_opt_config(cfg, ctx)
     check_prox_config(cfg, config_name, backend)
+    check_hetero_config(cfg)
     if cfg.clients_per_gpu > 1:
-        kw = dict(prox_mu=cfg.prox_mu, partition=cfg.client_partition, shards_per_client=cfg.client_shards,
+        kw = dict(dirichlet_alpha=cfg.client_alpha, local_epochs=cfg.local_epochs, aggregate=cfg.aggregate,
+                  prox_mu=cfg.prox_mu, partition=cfg.client_partition, shards_per_client=cfg.client_shards,
                   clients=cfg.clients_per_gpu, cohort=cohort_size(cfg), lr=cfg.lr, momentum=cfg.momentum, seed=seed,
                   client_dp_clip=cfg.client_dp_clip, client_dp_noise=cfg.client_dp_noise, client_dp_seed=mix64(seed),
                   server_lr=cfg.server_lr, world_size=client_dp_world(cfg, ctx), server_opt=cfg.server_opt,
@@ -468,6 +520,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         check_prox_config(cfg, cname, pick_backend(cfg, cname, ctx))
     check_client_dp_config(cfg)
     check_server_opt_config(cfg, ctx)
+    check_hetero_config(cfg)
     M = cohort_size(cfg)  # clients trained per GPU and round (1: no client sampling)
     all_rows: List[Dict] = []
     fcomm = FedAvgComm(ctx)
@@ -508,6 +561,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         evals = []  # (round, summed record, this rank's eval_ms) per evaluated round
         privacy = []  # DP-SGD: this client's cumulative (round, steps, epsilon)
         cohorts = []  # client sampling: (round, this rank's drawn client ids)
+        shapes = []  # unequal clients: (round, this rank's cohort sizes, steps, weights)
+        hetero = hetero_on(cfg) and cfg.clients_per_gpu > 1
         client_privacy = []  # client-level DP, rank 0: (round, median client norm, clipped share)
         sample_rate = cfg.batch_size / x.shape[0]
         for r in range(start_round, cfg.rounds):
@@ -545,6 +600,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
             m_l1 = fcomm.mark()
             if cfg.clients_per_gpu > 1:
                 cohorts.append((r, list(trainer.round_clients)))
+                if hetero:
+                    shapes.append((r,) + tuple(list(v) for v in trainer.last_round_shape()))
             if cfg.dp_clip > 0:
                 privacy.append((r, trainer.dp_steps,
                                 dp_epsilon(cfg.dp_noise, sample_rate, trainer.dp_steps, cfg.dp_delta)))
@@ -572,7 +629,9 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                     with fround.averaged_in_place():  # delayed: avg_r saved, the stale correction stays pending
                         save_checkpoint(ckpt_path(cfg.ckpt_dir, r, cname), r, model, mom, cname, asdict(cfg))
                 save_rank_state(cfg.ckpt_dir, r, cname, ctx.rank, trainer, client_weights=own)
-            recs.append((r, rec, m_l0, m_l1, inner, avg_loss, (time.perf_counter() - t_round0) * 1e3))
+            # windows the round trained on: B * sum_k S_k with unequal local work
+            windows = cfg.batch_size * (sum(shapes[-1][2]) if hetero else M * cfg.local_steps)
+            recs.append((r, rec, m_l0, m_l1, inner, avg_loss, (time.perf_counter() - t_round0) * 1e3, windows))
             if cfg.client_dp_clip > 0 and ctx.rank == 0:  # (avg_loss synchronised: the round's norms are there)
                 norms, clipped = trainer.last_clip_stats()
                 client_privacy.append((r, float(np.median(norms)), clipped))
@@ -586,11 +645,11 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         fround.finalize()
         _sync(dev)
         rows = []
-        for r, rec, m_l0, m_l1, inner, avg_loss, wall_ms in recs:
+        for r, rec, m_l0, m_l1, inner, avg_loss, wall_ms, windows in recs:
             local_ms = m_l0.ms_to(m_l1) - sum(a.ms_to(b) for a, b in inner)
             row = RoundStats(config=cname, world_size=ctx.world_size, rank=ctx.rank, round_idx=r,
                              batch_size=cfg.batch_size, local_steps=cfg.local_steps, local_train_ms=local_ms,
-                             comm_ms=rec.comm_ms(), samples_per_s=M * cfg.batch_size * cfg.local_steps / (local_ms / 1e3),
+                             comm_ms=rec.comm_ms(), samples_per_s=windows / (local_ms / 1e3),
                              avg_loss=avg_loss, comm_exposed_ms=rec.exposed_ms(), round_wall_ms=wall_ms,
                              backend=backend, overlap=(cfg.overlap if not weighted else "none")
                              if cfg.sync == "fedavg" else cfg.sync)
@@ -636,6 +695,11 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                 append_results(crows, cfg.cohort_csv, COHORT_COLUMNS)
             for row in crows:
                 log.event("cohort", **row)
+        if shapes and ctx.rank == 0:
+            for r, sizes, steps, weights in shapes:
+                log.event("cohort_shape", config=cname, round_idx=r, partition=cfg.client_partition,
+                          client_alpha=cfg.client_alpha, local_epochs=cfg.local_epochs, aggregate=cfg.aggregate,
+                          sizes_rank0=sizes, steps_rank0=steps, weights_rank0=weights)
         if client_privacy:
             cprows = [{"config": cname, "world_size": ctx.world_size, "round_idx": r,
                        "sample_rate": M / cfg.clients_per_gpu, "noise_multiplier": cfg.client_dp_noise,
@@ -665,7 +729,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
 
 
 def summarize(rows: List[Dict], cname: str, world: int, log: RankLogger, cohort: int = 1) -> Dict[str, float]:
-    """``cohort``: clients trained per GPU and round - a row's windows are cohort * batch_size * local_steps."""
+    """``cohort``: clients trained per GPU and round - a row's windows are cohort * batch_size * local_steps, or the
+    ``B * sum_k S_k`` its ``samples_per_s`` counts when the clients' local steps differ."""
     if not rows:
         return {}
     rounds = sorted({r["round_idx"] for r in rows})
@@ -674,7 +739,8 @@ def summarize(rows: List[Dict], cname: str, world: int, log: RankLogger, cohort:
     for ri in rounds:
         rr = [r for r in rows if r["round_idx"] == ri]
         wall = max(r["round_wall_ms"] for r in rr) / 1e3
-        node += sum(cohort * r["batch_size"] * r["local_steps"] for r in rr) / wall
+        # (a row's windows: cohort * batch_size * local_steps, fewer with --local-epochs - samples_per_s counts them)
+        node += sum(round(r["samples_per_s"] * r["local_train_ms"] / 1e3) for r in rr) / wall
     node /= len(rounds)
     comm = float(np.mean([r["comm_ms"] for r in rows]))
     local = float(np.mean([r["local_train_ms"] for r in rows]))

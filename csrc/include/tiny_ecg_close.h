@@ -25,12 +25,15 @@ struct CohortClose {
   float* m;
   float* v;
   float* delta;
+  // (nullable) [M] fp32 on the device: Delta = sum_c weight[c] * d_c in place of the mean (cohort_delta_wscale_kernel
+  // folds it into scale[], and inv_M is 1); not with a clip norm
+  const float* weight;
 };
 
 // kOk, or kBadArg for a close that cohort_close must not be given.
 int check_cohort_close(const CohortClose& c);
 
-// The two launches of a checked close: cohort_delta_scale_kernel, then cohort_delta_kernel (``delta`` set),
+// The two launches of a checked close: cohort_delta_scale_kernel (``weight`` set: cohort_delta_wscale_kernel), then cohort_delta_kernel (``delta`` set),
 // cohort_server_opt_kernel<opt> (opt != 0) or cohort_dp_mean_kernel.
 int cohort_close(const CohortClose& c, hipStream_t stream);
 

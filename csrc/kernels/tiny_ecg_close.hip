@@ -75,6 +75,34 @@ __global__ __launch_bounds__(WAVES * 64) void cohort_delta_scale_kernel(
   }
 }
 
+// cohort_delta_scale_kernel's sibling for a weighted close: norms, clip factor and the advance of the round word are
+// its lines; the one difference is scale[c] = s_c * weight[c] (``weight`` [M] fp32 on the device: a cohort's weights
+// change per round, and kernel arguments are baked into a captured graph).  The kernels below then form
+// Delta_i = sum_c (s_c w_c) d_c[i] with inv_M = 1.
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void cohort_delta_wscale_kernel(
+    const float* __restrict__ params, const float* __restrict__ global_params, int P, int M, float clip,
+    float* __restrict__ scale, float* __restrict__ norm, unsigned long long* __restrict__ round_word,
+    const float* __restrict__ weight) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) round_word[0] = round_word[0] + 1ull;
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (c >= M) return;  // wave-uniform
+  const float* p = params + (long)c * cohort_pstride(P);
+  float ss = 0.f;
+  for (int i = lane; i < P; i += 64) {
+    const float d = p[i] - global_params[i];
+    ss += d * d;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  if (lane == 0) {
+    const float n = sqrtf(ss);
+    norm[c] = n;
+    scale[c] = (n > 0.f ? fminf(1.f, clip / n) : 1.f) * weight[c];
+  }
+}
+
 // Delta_i in two parts, shared by the three kernels below (one thread per parameter): the noise nu * z_i, drawn first,
 // under the latency of the loads that follow, and the clipped mean plus that noise.  Each kernel loads g - and its
 // server state - between the two: that order is the kernels' schedule.
@@ -220,6 +248,8 @@ int ecg::tiny::check_cohort_close(const CohortClose& c) {
   if (!c.params || !c.global || !c.round_word || !c.scale || !c.norm) return ecg::kBadArg;
   if (c.P < 1 || c.M < 1 || c.M > 65535) return ecg::kBadArg;  // a cohort's range (M is a grid extent of its rounds)
   if (c.clip < 0.f || c.sigma < 0.f || c.server_lr < 0.f || (c.sigma > 0.f && c.clip == 0.f)) return ecg::kBadArg;
+  // the sensitivity of a weighted, clipped mean is not C / M, and no accountant here covers it
+  if (c.weight && c.clip > 0.f) return ecg::kBadArg;
   if (c.delta) return ecg::kOk;  // the split close reads neither the optimizer nor its state
   return c.opt != 0 ? check_server_opt(c.opt, c.beta1, c.beta2, c.tau, c.m, c.v) : ecg::kOk;
 }
@@ -230,13 +260,18 @@ int ecg::tiny::check_cohort_close(const CohortClose& c) {
 // (train/cohort.py does): 2^-24 of the noise, far below the Box-Muller difference between device and host.
 int ecg::tiny::cohort_close(const CohortClose& c, hipStream_t stream) {
   const float nu = (float)((double)c.sigma * (double)c.clip / (double)c.M);
-  const float eta = c.server_lr == 0.f ? 1.f : c.server_lr, inv_M = 1.0f / (float)c.M;
+  const float eta = c.server_lr == 0.f ? 1.f : c.server_lr, inv_M = c.weight ? 1.0f : 1.0f / (float)c.M;
   const float* scale = c.scale;
   const unsigned long long* word = c.round_word;
-  hipLaunchKernelGGL(cohort_delta_scale_kernel<CDP_CLIENTS_PER_BLOCK>,
-                     dim3((c.M + CDP_CLIENTS_PER_BLOCK - 1) / CDP_CLIENTS_PER_BLOCK), dim3(CDP_CLIENTS_PER_BLOCK * 64),
-                     0, stream, c.params, (const float*)c.global, c.P, c.M, c.clip > 0.f ? c.clip : FLT_MAX, c.scale,
-                     c.norm, c.round_word);
+  const dim3 sgrid((c.M + CDP_CLIENTS_PER_BLOCK - 1) / CDP_CLIENTS_PER_BLOCK), sblock(CDP_CLIENTS_PER_BLOCK * 64);
+  if (c.weight)  // the weights are folded into scale[]: the second kernel is the one of an unweighted close
+    hipLaunchKernelGGL(cohort_delta_wscale_kernel<CDP_CLIENTS_PER_BLOCK>, sgrid, sblock, 0, stream, c.params,
+                       (const float*)c.global, c.P, c.M, c.clip > 0.f ? c.clip : FLT_MAX, c.scale, c.norm, c.round_word,
+                       c.weight);
+  else
+    hipLaunchKernelGGL(cohort_delta_scale_kernel<CDP_CLIENTS_PER_BLOCK>, sgrid, sblock, 0, stream, c.params,
+                       (const float*)c.global, c.P, c.M, c.clip > 0.f ? c.clip : FLT_MAX, c.scale, c.norm,
+                       c.round_word);
   ECG_HIP_CHECK(hipGetLastError());
   const dim3 grid((c.P + 255) / 256), block(256);
 #define ECG_SERVER_OPT_LAUNCH(OPT)                                                                                 \
@@ -309,6 +344,19 @@ ECG_API int ecg_cohort_delta_close(const float* params, const float* global, int
   if (!delta) return ecg::kBadArg;
   return close_entry(nc, {params, const_cast<float*>(global), 0, M, clip, sigma, 0.f, seed, round_word, scale, norm, 0,
                           0.f, 0.f, 0.f, nullptr, nullptr, delta}, stream);
+}
+
+// The weighted close on caller-supplied buffers: Delta = sum_c weight[c] * (p_c - g) in ascending order (``weight`` [M]
+// fp32, device; no clip, no noise), then the plain step (``opt`` 0), a server optimizer (1..4, as
+// ecg_cohort_server_close) or, with ``delta`` non-null, the split close (``global`` is only read; opt, m, v are not).
+// ``scale`` receives the weights as the second kernel reads them, ``norm`` the delta norms.
+ECG_API int ecg_cohort_weighted_close(const float* params, float* global, int nc, int M, const float* weight,
+                                      float server_lr, unsigned long long* round_word, float* scale, float* norm,
+                                      int opt, float b1, float b2, float tau, float* m, float* v, float* delta,
+                                      hipStream_t stream) {
+  if (!weight) return ecg::kBadArg;
+  return close_entry(nc, {params, global, 0, M, 0.f, 0.f, server_lr, 0ull, round_word, scale, norm, opt, b1, b2, tau, m,
+                          v, delta, weight}, stream);
 }
 
 // One server step on ``g`` [n] from ``delta`` [n] (the second half of the split close, after the caller averaged the

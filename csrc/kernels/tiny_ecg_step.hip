@@ -1315,12 +1315,18 @@ __device__ inline float dp_normal(int i, unsigned long long seed, unsigned long 
 // mu/2 * |w - anchor|^2: d = gsum + wd * p + mu * (p - a), which then passes through momentum and nesterov like any
 // other gradient (torch.optim.SGD with mu * (p - a) added to p.grad).  ``anchor`` [P] is shared by all clients of a cohort
 // (never offset by the client stride); the updating thread loads it beside p0 / m0, before the slab reads.
-template <int RED_COLS, bool DP, bool COHORT, bool PROX = false>
+// STEPS (COHORT only; clients with unequal local work): a block of client c returns at once when ``step`` >=
+// client_steps[c] ([M] int32 on the device: a cohort is drawn per round, and kernel arguments are baked into a captured
+// graph) - before any parameter, momentum, anchor or slab load and before the barrier; the condition is block-uniform.
+// A client that has finished its local steps is thereby frozen: its weights, momentum, image and loss word are not
+// written, while the step kernel still fills its slab rows and the gather blocks, which leave above, still run.
+template <int RED_COLS, bool DP, bool COHORT, bool PROX = false, bool STEPS = false>
 __device__ __forceinline__ void slab_reduce_body(
     const float* slab, float* params, float* mom, int nred, int G, int stride, int P, int flags, float momentum,
     float lr, float wd, unsigned char* wprep, float* loss_acc, float* grad_out, const float* scale, float noise_scale,
     unsigned long long seed, const unsigned long long* dp_step, const GatherArgs& ga, const float* anchor = nullptr,
-    float mu = 0.f) {
+    float mu = 0.f, const int* client_steps = nullptr, int step = 0) {
+  static_assert(!STEPS || COHORT, "per-client step counts exist in the cohort form only");
   constexpr int NT = RED_COLS * RED_ROWG;
   const int apply = COHORT ? 1 : flags & kRedApply, nesterov = flags & kRedNesterov;
   if ((int)blockIdx.x >= nred) {  // block-uniform: gather blocks never reach the barrier below
@@ -1331,6 +1337,8 @@ __device__ __forceinline__ void slab_reduce_body(
   if constexpr (COHORT) {
     const int nblk = (P + RED_COLS) / RED_COLS;  // blocks per client: columns 0 .. P
     client = blk / nblk;
+    if constexpr (STEPS)
+      if (step >= client_steps[client]) return;  // block-uniform, before the barrier: a frozen client
     const int pstride = cohort_pstride(P);
     slab += (long)client * G * stride;
     params += (long)client * pstride;
@@ -1516,6 +1524,31 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_prox_s
     GatherArgs ga) {
   slab_reduce_body<RED_COLS, false, true, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
                                                 loss_acc, nullptr, nullptr, 0.f, 0ull, nullptr, ga, anchor, mu);
+}
+
+// ---------------------------------------------------------------------------- per-client local steps
+// slab_reduce_body's STEPS form of the two cohort kernels: their argument lists with ``client_steps`` [M], ``step`` in
+// front of ``ga``.  With every client_steps[c] > step they leave the bits of the kernels above.
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_steps_sgd_kernel(
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
+    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, const int* __restrict__ client_steps, int step,
+    GatherArgs ga) {
+  slab_reduce_body<RED_COLS, false, true, false, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd,
+                                                       wprep, loss_acc, nullptr, nullptr, 0.f, 0ull, nullptr, ga,
+                                                       nullptr, 0.f, client_steps, step);
+}
+
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_steps_prox_sgd_kernel(
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
+    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, const float* __restrict__ anchor, float mu,
+    const int* __restrict__ client_steps, int step, GatherArgs ga) {
+  slab_reduce_body<RED_COLS, false, true, true, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd,
+                                                      wprep, loss_acc, nullptr, nullptr, 0.f, 0ull, nullptr, ga, anchor,
+                                                      mu, client_steps, step);
 }
 
 // anchor[0:P] = params[0:P]: the first launch of a single client's FedProx round.
@@ -1809,17 +1842,27 @@ int cohort_step_dispatch(int prec, const StepArgs& a, int M, hipStream_t stream)
 }
 
 // The cohort reduce + SGD of one step: M x the plain reduce's blocks, then the gather blocks of the next step.
-// FedProx as in reduce_dispatch, one anchor for all M clients.
+// FedProx as in reduce_dispatch, one anchor for all M clients.  ``client_steps`` (nullable, [M] on the device) with
+// ``step``: the STEPS form of either kernel; null: the launches of before.
 int cohort_reduce_dispatch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
                            float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
                            hipStream_t stream, const GatherArgs* gather = nullptr, const float* anchor = nullptr,
-                           float mu = 0.f, bool prox = false) {
+                           float mu = 0.f, bool prox = false, const int* client_steps = nullptr, int step = 0) {
   prox = prox || mu != 0.f;
   int st = check_reduce(G, stride, P, 1, params, momentum, mom);
   if (!st && prox) st = check_prox(anchor, mu);
+  if (!st && client_steps && step < 0) st = ecg::kBadArg;
   if (st) return st;
   const RedGeom g = red_geom(P, M, gather, true);
-  if (prox)
+  if (client_steps && prox)
+    hipLaunchKernelGGL(slab_reduce_cohort_steps_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0,
+                       stream, slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep,
+                       loss_acc, anchor, mu, client_steps, step, g.ga);
+  else if (client_steps)
+    hipLaunchKernelGGL(slab_reduce_cohort_steps_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream,
+                       slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
+                       client_steps, step, g.ga);
+  else if (prox)
     hipLaunchKernelGGL(slab_reduce_cohort_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream,
                        slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
                        anchor, mu, g.ga);
@@ -1952,6 +1995,19 @@ ECG_API int ecg_slab_reduce_cohort_prox_sgd(const float* slab, int G, int M, int
   if (!slab || M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
   return cohort_reduce_dispatch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov,
                                 static_cast<unsigned char*>(wprep), stream, nullptr, anchor, mu, true);
+}
+
+// ecg_slab_reduce_cohort_prox_sgd's twin with per-client step counts: the reduce of local step ``step`` (>= 0), which
+// leaves every client c with ``step`` >= client_steps[c] ([M] int32, device) as it is.  ``mu`` may be 0 (the plain
+// STEPS kernel; ``anchor`` is then not looked at).
+ECG_API int ecg_slab_reduce_cohort_steps_sgd(const float* slab, int G, int M, int stride, int P, float* params,
+                                             float* mom, float* loss_acc, float lr, float momentum, float wd,
+                                             int nesterov, void* wprep, const float* anchor, float mu,
+                                             const int* client_steps, int step, hipStream_t stream) {
+  if (!slab || M < 1 || M > 65535 || !client_steps) return ecg::kBadArg;
+  return cohort_reduce_dispatch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov,
+                                static_cast<unsigned char*>(wprep), stream, nullptr, anchor, mu, false, client_steps,
+                                step);
 }
 
 // A local round: ``steps`` times "step kernel, then reduce + SGD kernel" (DP-SGD: step kernel, clip factors, clipped
@@ -2214,7 +2270,7 @@ ECG_API int ecg_tiny_cohort_wprep_stride(void) { return kCohortWprepStride; }
 // rows gathered by the previous reduce - and need wprep, xg, yg and xbg, sized for M * B rows
 // (ecg_tiny_gather_floats / _halfs(L, M * B)); fp32 rounds take none of them.  There is no DP-SGD in a cohort.
 // The close: with the cdp_* fields, server_lr, server_opt and server_delta all zero (server_lr 1 counts as zero) it is
-// cohort_mean_kernel; anything else is ecg::tiny::cohort_close (include/tiny_ecg_close.h), which picks its kernel by
+// cohort_mean_kernel; anything else - client_weight among it - is ecg::tiny::cohort_close (include/tiny_ecg_close.h), which picks its kernel by
 // server_delta, then server_opt.
 // ops/_lib.py mirrors this struct (TinyCohortRound) and checks its size against ecg_tiny_cohort_round_sizeof().
 struct EcgTinyCohortRound {
@@ -2261,6 +2317,17 @@ struct EcgTinyCohortRound {
   // ``global_params`` itself - the fan-out leaves the round's starting weights there and nothing writes them before
   // the close, whichever close it is, nor with fanout == 0.  prox_mu == 0: the launches of before.
   float prox_mu;
+  // Unequal local work (nullable): [M] int32 on the device, client c runs the first client_steps[c] of the round's
+  // ``steps`` local steps and is frozen for the rest (slab_reduce_body's STEPS form, with step = s in every step's
+  // reduce; the step launches and the gather do not change, so the ``idx`` rows of a frozen client's steps are still
+  // read and must be valid dataset rows).  The caller guarantees 1 <= client_steps[c] <= steps - device values cannot
+  // be range-checked here, and a bf16 round's first reduce is what writes a client's whole image.  Read when a
+  // round runs, not when it is captured: one graph serves every round's values.
+  const int* client_steps;
+  // A weighted close (nullable): [M] fp32 on the device, Delta = sum_c client_weight[c] * d_c in ascending order - the
+  // close is always ecg::tiny::cohort_close with these weights (CohortClose::weight), never cohort_mean_kernel.  It
+  // needs cdp_scale, cdp_norm and cdp_round and cdp_clip == 0.  Read when a round runs, like client_steps.
+  const float* client_weight;
 };
 
 ECG_API int ecg_tiny_cohort_round_sizeof(void) { return (int)sizeof(EcgTinyCohortRound); }
@@ -2275,7 +2342,8 @@ static bool cohort_dp_on(const EcgTinyCohortRound& r) {
 static CohortClose cohort_close_args(const EcgTinyCohortRound& r) {
   return {r.params,   r.global_params, make_layout(r.nc).P, r.M,           r.cdp_clip,    r.cdp_sigma,
           r.server_lr, r.cdp_seed,     r.cdp_round,         r.cdp_scale,   r.cdp_norm,    r.server_opt,
-          r.server_beta1, r.server_beta2, r.server_tau,     r.server_m,    r.server_v,    r.server_delta};
+          r.server_beta1, r.server_beta2, r.server_tau,     r.server_m,    r.server_v,    r.server_delta,
+          r.client_weight};
 }
 
 static int check_cohort_round(const EcgTinyCohortRound* r) {
@@ -2291,7 +2359,7 @@ static int check_cohort_round(const EcgTinyCohortRound* r) {
   const long rows = (long)r->M * r->B;
   if (rows * r->slab_stride * 4 > INT_MAX || rows * (pack_ldb(r->L) + 8) * 4 > INT_MAX) return ecg::kTooLarge;
   if (r->prox_mu < 0.f) return ecg::kBadArg;
-  if (cohort_dp_on(*r) || r->server_delta) return check_cohort_close(cohort_close_args(*r));
+  if (cohort_dp_on(*r) || r->server_delta || r->client_weight) return check_cohort_close(cohort_close_args(*r));
   // the plain mean reads none of the close's fields; a negative clip norm, or noise without a clip norm, is an error
   return (r->cdp_clip < 0.f || r->cdp_sigma != 0.f) ? ecg::kBadArg : ecg::kOk;
 }
@@ -2319,10 +2387,11 @@ static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream)
     int st = cohort_step_dispatch(r.prec, a, r.M, stream);
     if (st) return st;
     st = cohort_reduce_dispatch(r.slab, r.B, r.M, r.slab_stride, P, r.params, r.mom, r.loss_acc, r.lr, r.momentum, r.wd,
-                                r.nesterov, wprep, stream, gather_next ? &ga : nullptr, r.global_params, r.prox_mu);
+                                r.nesterov, wprep, stream, gather_next ? &ga : nullptr, r.global_params, r.prox_mu, false,
+                                r.client_steps, s);
     if (st) return st;
   }
-  if (cohort_dp_on(r) || r.server_delta) return cohort_close(cohort_close_args(r), stream);
+  if (cohort_dp_on(r) || r.server_delta || r.client_weight) return cohort_close(cohort_close_args(r), stream);
   hipLaunchKernelGGL(cohort_mean_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, r.params, r.global_params,
                      P, r.M, 1.0f / (float)r.M);
   ECG_HIP_CHECK(hipGetLastError());

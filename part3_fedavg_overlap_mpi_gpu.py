@@ -30,6 +30,10 @@ fused backend, with or without --clients-per-gpu, any model on the torch backend
 AMP or --overlap delayed)
 --client-partition {contiguous,shards} --client-shards s (needs --clients-per-gpu: "shards" deals every virtual client s
 runs of the GPU's label-sorted training windows - label-skewed, non-IID clients - instead of a contiguous slice)
+--client-partition dirichlet --client-alpha a --local-epochs E --aggregate {mean,weighted,nova} (need --clients-per-gpu:
+virtual clients of unequal sizes by the label-Dirichlet split, min(local steps, E passes over its own windows) local
+steps per client, and the cohort's deltas averaged with n_k / n or with FedNova's normalised weights; not with
+--client-dp-clip, nova not with --prox-mu)
 """
 from __future__ import annotations
 
