@@ -93,6 +93,11 @@ class FedAvgConfig:
     # aggregate mean | weighted (n_k / n over the cohort) | nova (FedNova's normalised averaging)
     local_epochs: int = 0
     aggregate: str = "mean"
+    # robust aggregates (need clients_per_gpu > 1): aggregate trimmed - the coordinate-wise mean of a cohort's deltas
+    # without the floor(trim_frac * M) smallest and largest (trim_frac in (0, 0.5), no default: 0 is "not given") - or
+    # median; flip_clients F > 0 mirrors the training labels of virtual clients 0..F-1 (poisoned clients)
+    trim_frac: float = 0.0
+    flip_clients: int = 0
     results_csv: str = "results/fedavg_results.csv"
     jsonl: Optional[str] = None
     model: str = "tiny_ecg"

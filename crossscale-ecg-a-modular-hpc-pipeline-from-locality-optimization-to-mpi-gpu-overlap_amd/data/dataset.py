@@ -359,6 +359,40 @@ def client_partition(partition: str, y: torch.Tensor, clients: int, shards_per_c
     return shard_partition(y, clients, shards_per_client, seed).to(device)
 
 
+def flip_client_labels(y: torch.Tensor, order: torch.Tensor, sizes: Optional[torch.Tensor], clients: int,
+                       nc: int) -> torch.Tensor:
+    """Poisoned clients by label flipping: a copy of the labels ``y`` [N] in which the training rows owned by clients
+    ``0 .. clients - 1`` - the first ``sizes[k]`` entries of row k of ``order`` (int64 ``[K, n]``; ``sizes`` None: all n)
+    - hold ``nc - 1 - y``.  Rows of other clients and rows no client owns (a partition's remainder, an evaluation
+    hold-out kept elsewhere) are as in ``y``.  A pure function: ``y`` is not modified, and applying it twice restores
+    the labels."""
+    F = int(clients)
+    if order.dim() != 2 or not 0 <= F <= order.shape[0]:
+        raise ValueError(f"need order [K, n] and 0 <= clients <= K, got {tuple(order.shape)} and {F}")
+    out = y.clone()
+    for k in range(F):
+        rows = order[k] if sizes is None else order[k, : int(sizes[k])]
+        rows = rows.to(y.device)
+        out[rows] = (int(nc) - 1) - y[rows]
+    return out
+
+
+def flipped_labels(y: torch.Tensor, order: Optional[torch.Tensor], sizes: Optional[torch.Tensor], clients: int,
+                   flip_clients: int, nc: int) -> torch.Tensor:
+    """The labels a cohort trainer of ``clients`` K virtual clients trains on: ``y`` itself for ``flip_clients`` F == 0,
+    else ``flip_client_labels`` for clients 0..F-1 of the partition ``order`` / ``sizes`` as ``CohortSampler`` takes them
+    (``order`` None: the contiguous partitions of ``N // K`` rows)."""
+    K, F = int(clients), int(flip_clients)
+    if not 0 <= F <= K:
+        raise ValueError(f"flip_clients must be in [0, clients = {K}], got {F}")
+    if F == 0:
+        return y
+    if order is None:
+        n = y.shape[0] // K
+        order = torch.arange(K * n, dtype=torch.int64, device=y.device).view(K, n)
+    return flip_client_labels(y, order, sizes, F, nc)
+
+
 class CohortSampler:
     """Client sampling for cohorts of virtual clients: which clients train in round ``r``, and on which rows.
 

@@ -83,7 +83,8 @@ class TinyCohortRound(C.Structure):
                 ("cdp_clip", f32), ("cdp_sigma", f32), ("server_lr", f32), ("cdp_seed", u64), ("cdp_scale", vp),
                 ("cdp_norm", vp), ("cdp_round", vp), ("server_opt", i32), ("server_beta1", f32), ("server_beta2", f32),
                 ("server_tau", f32), ("server_m", vp), ("server_v", vp), ("server_delta", vp),
-                ("prox_mu", f32), ("client_steps", vp), ("client_weight", vp)]
+                ("prox_mu", f32), ("client_steps", vp), ("client_weight", vp),
+                ("robust_trim", i32), ("robust_scratch", vp)]
 
 
 def _bind_kernels(lib: C.CDLL) -> None:
@@ -123,6 +124,8 @@ def _bind_kernels(lib: C.CDLL) -> None:
                                           vp])
     _sig(lib, "ecg_cohort_delta_close", [vp, vp, i32, i32, f32, f32, u64, vp, vp, vp, vp, vp])
     _sig(lib, "ecg_cohort_weighted_close", [vp, vp, i32, i32, vp, f32, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp, vp])
+    _sig(lib, "ecg_cohort_robust_close", [vp, vp, i32, i32, i32, f32, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp, vp,
+                                          vp])
     _sig(lib, "ecg_server_opt_step", [vp, vp, i64, i32, f32, f32, f32, f32, vp, vp, vp])
     _sig(lib, "ecg_tiny_cohort_param_stride", [i32])
     _sig(lib, "ecg_tiny_cohort_wprep_stride", [])

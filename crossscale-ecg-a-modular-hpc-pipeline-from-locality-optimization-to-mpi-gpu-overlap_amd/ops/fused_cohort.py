@@ -42,6 +42,14 @@ round's S steps and is frozen for the rest: the STEPS form of the cohort reduce,
 ``train.cohort.weights_of``.  Step counts and weights change with every round's cohort, so they live in device arrays
 the kernels read - one pair per index table, filled by ``stage()`` beside it - and one captured graph serves every
 round.  A weighted close takes no clip and no noise.
+
+Robust aggregates: ``robust`` "trimmed" (with ``trim_frac``) or "median" (beside ``aggregate``, which stays "mean") close the round with the coordinate-wise
+trimmed mean of the clients' deltas (``train.cohort.robust_delta`` states it, ``train.cohort.trim_count`` the k dropped at
+each end): ``cohort_delta_scale_kernel`` without a clip, ``cohort_robust_delta_kernel`` into ``server_delta`` (scope
+"global") or into a [P] scratch tensor this trainer owns, and from there ``server_step_kernel`` - the plain step or the
+server optimizer's.  k is a scalar in the round's description, baked into its graphs.  No clip, noise or weights; a cohort
+of at most 64; a robust aggregate alone leaves the reduce in its plain form (``client_steps`` stays null).
+``flip_clients`` F > 0 mirrors the training labels of clients 0..F-1 (``data.dataset.flip_client_labels``).
 """
 from __future__ import annotations
 
@@ -52,12 +60,12 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from ..data.dataset import CohortSampler, client_partition
+from ..data.dataset import CohortSampler, client_partition, flipped_labels
 from ..models.tiny_ecg import TinyECG, num_params
 from .fused_tiny import _check_dataset, labels_int32, prec_id, slab_stride
 from .tiny_eval import EvalResult, TinyEvaluator, tiny_evaluate
-from ..train.cohort import (check_aggregate, check_client_dp, client_dp_seed_of, client_dp_sigma_share,
-                            cohort_round_shape, load_server_state)
+from ..train.cohort import (check_aggregate, check_client_dp, check_robust, client_dp_seed_of,
+                            client_dp_sigma_share, cohort_round_shape, load_server_state, trim_count)
 from ..train.server_opt import BETA1, BETA2, TAU, check_server_opt, check_server_scope, server_opt_init
 
 
@@ -73,10 +81,14 @@ class FusedCohortTrainer:
                  server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
                  server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank",
                  prox_mu: float = 0.0, partition: str = "contiguous", shards_per_client: int = 2,
-                 dirichlet_alpha: float = 0.0, local_epochs: int = 0, aggregate: str = "mean"):
+                 dirichlet_alpha: float = 0.0, local_epochs: int = 0, aggregate: str = "mean",
+                 robust: str = "none", trim_frac: Optional[float] = None, flip_clients: int = 0):
         if not prox_mu >= 0.0:
             raise ValueError(f"prox_mu must be >= 0, got {prox_mu}")
         check_aggregate(aggregate, local_epochs, nesterov, prox_mu, client_dp_clip)
+        check_robust(robust, aggregate, client_dp_clip)
+        self.robust = robust
+        self.trim = trim_count(robust, clients if not cohort else int(cohort), trim_frac)  # 0: not a robust close
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients: the cohort "
                              "reduce has no per-sample clip")
@@ -93,8 +105,6 @@ class FusedCohortTrainer:
             raise ValueError("model and dataset must be on the same device")
         self.P = num_params(self.nc)
         self.x = x_gpu.contiguous()
-        self.y32 = labels_int32(y_gpu, self.nc)
-        _check_dataset(self.x, self.y32, self.nc)
         self.B, self.S = int(batch_size), int(steps_per_round)
         self.K = int(clients)
         self.M = self.K if not cohort else int(cohort)
@@ -105,6 +115,9 @@ class FusedCohortTrainer:
         order = client_partition(partition, y_gpu, self.K, self.shards_per_client, seed, self.device,
                                  alpha=self.dirichlet_alpha, min_rows=self.B)
         order, sizes = order if isinstance(order, tuple) else (order, None)
+        self.flip_clients = int(flip_clients)
+        self.y32 = labels_int32(flipped_labels(y_gpu, order, sizes, self.K, self.flip_clients, self.nc), self.nc)
+        _check_dataset(self.x, self.y32, self.nc)
         self.sampler = CohortSampler(self.x.shape[0], self.B, self.S, self.K, self.M, self.device, seed=seed,
                                      order=order, sizes=sizes)
         self.prox_mu = float(prox_mu)
@@ -162,7 +175,9 @@ class FusedCohortTrainer:
         split = self.server_scope == "global"
         self.server_delta = torch.zeros(self.P, **f32) if split else None
         self.client_dp = (self.cdp_clip > 0.0 or self.server_lr != 1.0 or server_opt != "none" or split
-                          or aggregate != "mean")
+                          or aggregate != "mean" or self.trim > 0)
+        # a robust close that is not split: Delta passes through this buffer on its way to server_step_kernel
+        self.robust_scratch = torch.zeros(self.P, **f32) if (self.trim > 0 and not split) else None
         self.cdp_scale = self.cdp_norm = self.cdp_round = None
         if self.client_dp:
             self.cdp_scale = torch.ones(self.M, **f32)
@@ -180,6 +195,8 @@ class FusedCohortTrainer:
             r.cdp_clip, r.cdp_sigma = self.cdp_clip, client_dp_sigma_share(self.cdp_noise, world_size)
             r.server_lr, r.cdp_seed = self.server_lr, self.cdp_seed
             r.cdp_scale, r.cdp_norm, r.cdp_round = (t.data_ptr() for t in (self.cdp_scale, self.cdp_norm, self.cdp_round))
+        if self.trim > 0:
+            self._round.robust_trim, self._round.robust_scratch = self.trim, _lib.ptr(self.robust_scratch)
         if split:  # (the struct's server_opt stays 0: apply_server_step takes the step, outside the round)
             self._round.server_delta = self.server_delta.data_ptr()
         elif self.server_opt_id:

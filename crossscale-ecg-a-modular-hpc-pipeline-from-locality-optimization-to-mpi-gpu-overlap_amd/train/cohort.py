@@ -39,6 +39,16 @@ al., "Tackling the Objective Inconsistency Problem in Heterogeneous Federated Op
 above, ``1 / M`` each.  Delta then takes the server step or the split close exactly as the unweighted one does; there is
 no clip and no noise on a weighted Delta (its sensitivity is not C / M).  ``cohort_delta_wscale_kernel`` and the STEPS
 form of the cohort reduce implement these definitions.  Every rank normalises over its own cohort.
+
+Robust aggregates (``robust`` "trimmed" with ``trim_frac``, or "median"; Yin et al., "Byzantine-Robust Distributed
+Learning"; an argument of its own beside ``aggregate``, which names the clients' weights and stays "mean" - a robust
+estimate takes none; the driver's ``--aggregate trimmed | median`` sets it): Delta_i is the coordinate-wise trimmed mean of the clients' ``d_c[i]`` - ``robust_delta`` below states it,
+``trim_count`` gives the k clients dropped at each end - and then takes the server step or the split close like every
+other Delta.  No clip, no noise, no weight; a cohort of at most 64 clients (``cohort_robust_delta_kernel`` holds a
+parameter's clients in the lanes of one wave); "median" with M <= 2 has k == 0 and is the mean.  Every rank trims within
+its own cohort: W ranks end on the mean of W robust estimates, not on one estimate over all W * M clients.
+``flip_clients`` F > 0 (``data.dataset.flip_client_labels``): the training labels of clients 0..F-1 are mirrored - the
+poisoned clients a robust aggregate is there for.
 """
 from __future__ import annotations
 
@@ -50,7 +60,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..data.dataset import CohortSampler, client_partition
+from ..data.dataset import CohortSampler, client_partition, flipped_labels
 from ..utils import philox
 from .local import add_prox_grad, check_prox
 from .server_opt import (BETA1, BETA2, TAU, check_server_opt, check_server_scope, server_opt_init,
@@ -66,9 +76,13 @@ class TorchCohortTrainer:
                  server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
                  server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank",
                  prox_mu: float = 0.0, partition: str = "contiguous", shards_per_client: int = 2,
-                 dirichlet_alpha: float = 0.0, local_epochs: int = 0, aggregate: str = "mean"):
+                 dirichlet_alpha: float = 0.0, local_epochs: int = 0, aggregate: str = "mean",
+                 robust: str = "none", trim_frac: Optional[float] = None, flip_clients: int = 0):
         check_prox(prox_mu, amp_dtype, model)
         check_aggregate(aggregate, local_epochs, nesterov, prox_mu, client_dp_clip)
+        check_robust(robust, aggregate, client_dp_clip)
+        self.robust = robust
+        self.trim = trim_count(robust, clients if not cohort else int(cohort), trim_frac)
         self.prox_mu = float(prox_mu)
         if dp_clip > 0.0:
             raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients")
@@ -88,6 +102,9 @@ class TorchCohortTrainer:
         order = client_partition(partition, y, self.K, self.shards_per_client, seed, self.device,
                                  alpha=self.dirichlet_alpha, min_rows=self.B)
         order, sizes = order if isinstance(order, tuple) else (order, None)
+        self.flip_clients = int(flip_clients)
+        nc = getattr(model, "num_classes", None) or int(y.max()) + 1
+        self.y = y = flipped_labels(y, order, sizes, self.K, self.flip_clients, nc)
         self.sampler = CohortSampler(x.shape[0], self.B, self.S, self.K, self.M, self.device, seed=seed, order=order,
                                      sizes=sizes)
         self._shape: Tuple[List[int], List[int], List[float]] = ([], [], [])
@@ -113,7 +130,7 @@ class TorchCohortTrainer:
         self.server_delta = (torch.zeros(numel, dtype=torch.float32, device=self.device)
                              if self.server_scope == "global" else None)
         self.client_dp = (self.cdp_clip > 0.0 or self.server_lr != 1.0 or server_opt != "none"
-                          or self.server_delta is not None)
+                          or self.server_delta is not None or self.trim > 0)
         self._norms: List[float] = []
         self._scales: List[float] = []
 
@@ -187,7 +204,8 @@ class TorchCohortTrainer:
         g = torch.cat([p.detach().reshape(-1) for p in self.model.parameters()]).float()
         acc, self._norms, self._scales = None, [], []
         for j in range(self.M):
-            d = torch.cat([p.reshape(-1) for p in self._client_round(j, self._steps[j], table)]).float() - g
+            pc = torch.cat([p.reshape(-1) for p in self._client_round(j, self._steps[j], table)]).float()
+            d = pc - g
             nrm = torch.linalg.vector_norm(d)
             sc = torch.ones((), **f32)
             if self.cdp_clip > 0.0 and float(nrm) > 0.0:
@@ -196,8 +214,15 @@ class TorchCohortTrainer:
             self._scales.append(float(sc))
             if weights is not None:
                 sc = sc * torch.tensor(weights[j], **f32)
-            acc = sc * d if acc is None else acc + sc * d
-        upd = acc * torch.tensor(1.0 if weights is not None else 1.0 / self.M, **f32)
+            if self.trim > 0:  # the robust close takes the clients' weights themselves, every one of them
+                acc = [] if acc is None else acc
+                acc.append(pc)
+            else:
+                acc = sc * d if acc is None else acc + sc * d
+        if self.trim > 0:
+            upd = robust_delta(torch.stack(acc), g, self.trim)
+        else:
+            upd = acc * torch.tensor(1.0 if weights is not None else 1.0 / self.M, **f32)
         if self.cdp_nu != 0.0:
             z = philox.normal(self.cdp_seed, r, g.numel(), stream=1).astype(np.float32)
             upd = upd + torch.tensor(self.cdp_nu, **f32) * torch.from_numpy(z).to(self.device)
@@ -272,7 +297,9 @@ def load_server_state(trainer, st: Dict[str, torch.Tensor]) -> None:
         t.copy_(st[key].to(t.device))
 
 
-AGGREGATES = ("mean", "weighted", "nova")
+AGGREGATES = ("mean", "weighted", "nova")  # the clients' weights in Delta = sum_c w_c d_c (weights_of)
+ROBUST_AGGREGATES = ("trimmed", "median")  # the robust estimates: Delta = robust_delta with trim_count's k, no weights
+ROBUST_MAX_COHORT = 64  # check_cohort_close's bound: cohort_robust_delta_kernel holds a parameter's clients in one wave
 
 
 def check_aggregate(aggregate: str, local_epochs: int, nesterov: bool, prox_mu: float, client_dp_clip: float) -> None:
@@ -286,6 +313,96 @@ def check_aggregate(aggregate: str, local_epochs: int, nesterov: bool, prox_mu: 
     if aggregate == "nova" and (nesterov or prox_mu > 0.0):
         raise ValueError('aggregate "nova" is not combined with nesterov momentum or FedProx (prox_mu > 0): its '
                          "normaliser a_c is derived for heavy-ball momentum SGD only")
+
+
+def check_robust(robust: str, aggregate: str, client_dp_clip: float) -> None:
+    if robust not in ("none",) + ROBUST_AGGREGATES:
+        raise ValueError(f"robust must be one of {['none'] + list(ROBUST_AGGREGATES)}, got {robust!r}")
+    if robust == "none":
+        return
+    if aggregate != "mean":
+        raise ValueError(f"robust {robust!r} is not combined with aggregate {aggregate!r}: a trimmed mean takes no "
+                         "client weights")
+    if client_dp_clip > 0.0:
+        raise ValueError(f"robust {robust!r} is not combined with client-level DP (client_dp_clip > 0): the "
+                         "sensitivity of a trimmed mean is not C / M, and no accountant here covers it")
+
+
+def trim_count(aggregate: str, cohort: int, trim_frac: Optional[float] = None) -> int:
+    """k, the clients a robust aggregate drops at each end of every parameter's order, for a cohort of M: "trimmed"
+    ``floor(trim_frac * M)`` with ``0 < trim_frac < 0.5`` (so 2 k < M), rejected when that is 0; "median"
+    ``(M - 1) // 2`` - the middle value for odd M, the mean of the two middle ones for even M, and 0, the plain mean,
+    for M <= 2; 0 for "none" and the names of ``AGGREGATES``.  ``trim_frac`` belongs to "trimmed" alone and has no
+    default."""
+    M = int(cohort)
+    if aggregate not in ("none",) + AGGREGATES + ROBUST_AGGREGATES:
+        raise ValueError(f"aggregate must be one of {list(AGGREGATES + ROBUST_AGGREGATES)}, got {aggregate!r}")
+    if M < 1:
+        raise ValueError(f"a cohort has at least one client, got {M}")
+    if aggregate != "trimmed" and trim_frac is not None:
+        raise ValueError(f'trim_frac is the share aggregate "trimmed" drops at each end: aggregate {aggregate!r} takes '
+                         "none")
+    if aggregate not in ROBUST_AGGREGATES:
+        return 0
+    if M > ROBUST_MAX_COHORT:
+        raise ValueError(f"aggregate {aggregate!r} needs a cohort of at most {ROBUST_MAX_COHORT} clients, got {M}: the "
+                         "selection kernel holds one parameter's clients in the lanes of one wave")
+    if aggregate == "median":
+        return (M - 1) // 2
+    if trim_frac is None:
+        raise ValueError('aggregate "trimmed" needs trim_frac, the share of the cohort dropped at each end: there is '
+                         "no default")
+    f = float(trim_frac)
+    if not 0.0 < f < 0.5:
+        raise ValueError(f"trim_frac must be in (0, 0.5), got {f:g}")
+    k = int(math.floor(f * M))
+    if k == 0:
+        raise ValueError(f"trim_frac {f:g} of a cohort of {M} drops floor({f:g} * {M}) = 0 clients: that is the plain "
+                         'mean - use aggregate "mean", a larger trim_frac or a larger cohort')
+    return k
+
+
+def _order_keys(x: torch.Tensor) -> torch.Tensor:
+    """The 32-bit keys (as int64) that order fp32 values as -inf < ... < -0 < +0 < ... < +inf < NaN: a NaN of either
+    sign 0xFFFFFFFF, else the bit pattern with the sign bit flipped (non-negative sign) or all bits flipped."""
+    b = x.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    key = torch.where((b >> 31) != 0, b ^ 0xFFFFFFFF, b ^ 0x80000000)
+    return torch.where(torch.isnan(x), torch.full_like(key, 0xFFFFFFFF), key)
+
+
+def robust_delta(stack: torch.Tensor, g: torch.Tensor, k: int) -> torch.Tensor:
+    """The coordinate-wise trimmed mean of M clients' round deltas, the definition ``cohort_robust_delta_kernel``
+    implements: ``stack`` [M, P] the clients' weights p_c, ``g`` [P] the round's starting weights, ``1 <= k``, ``2 k < M``.
+
+    ``x_c = p_c - g`` in fp32.  The M values of a parameter are ordered by ``_order_keys``, ties by client index:
+    ``rank_c = #{j : key_j < key_c, or key_j == key_c and j < c}``, a permutation of 0..M-1.  Client c is kept when
+    ``k <= rank_c < M - k``, and ``Delta = (((x_c1 + x_c2) + ...) + x_cn) * fp32(1 / n)`` over the ``n = M - 2 k`` kept
+    clients in ascending client order, every sum and the product rounded on its own in fp32.  (The running sum starts
+    from -0, for which ``-0 + x`` is x bit for bit.)  Integer keys, ranks, selects and sequential adds: on the CPU this
+    yields the kernel's bits.  At most k bad clients (NaN, +-inf) at a parameter are trimmed away; more propagate."""
+    M, k = int(stack.shape[0]), int(k)
+    if stack.dim() != 2 or g.shape != stack.shape[1:] or not (k >= 1 and 2 * k < M):
+        raise ValueError(f"need stack [M, P], g [P] and 1 <= k, 2 k < M; got {tuple(stack.shape)}, {tuple(g.shape)}, k {k}")
+    x = stack.float() - g.float()
+    key = _order_keys(x)
+    c = torch.arange(M, device=x.device)[:, None]
+    rank = torch.zeros_like(key)
+    for j in range(M):
+        rank += ((key[j] < key) | ((key[j] == key) & (j < c))).to(torch.int64)
+    kept = (rank >= k) & (rank < M - k)
+    s = torch.full_like(x[0], -0.0)
+    for j in range(M):
+        s = torch.where(kept[j], s + x[j], s)
+    one = torch.ones((), dtype=torch.float32, device=x.device)
+    return s * (one / (M - 2 * k))
+
+
+def robust_delta_f64(stack: torch.Tensor, g: torch.Tensor, k: int) -> torch.Tensor:
+    """``robust_delta`` in plain float64: the deltas sorted per parameter (NaN largest), k dropped at each end, the mean
+    of the rest.  [P] float64."""
+    M, k = int(stack.shape[0]), int(k)
+    x = torch.sort(stack.double() - g.double(), dim=0).values  # (torch orders NaN above +inf)
+    return x[k:M - k].mean(dim=0)
 
 
 def nova_norm(tau: int, rho: float) -> float:

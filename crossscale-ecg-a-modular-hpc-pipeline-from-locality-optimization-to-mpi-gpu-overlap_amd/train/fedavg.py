@@ -89,6 +89,15 @@ MI355X execution (vs the reference's host-staged per-tensor MPI calls and per-st
     sizes, steps and weights; no CSV and no checkpoint changes (all three are functions of (seed, round)).  Every rank
     normalises over its own cohort, so under ``--sync fedavg`` the all-reduce(AVG) gives every rank's cohort the same
     total weight, whatever its share of the windows.
+  * ``--aggregate {trimmed,median}`` / ``--trim-frac f`` / ``--flip-clients F`` (need ``--clients-per-gpu``): robust
+    aggregation.  ``trimmed`` drops the ``floor(f * M)`` smallest and largest of a cohort's M deltas per parameter and
+    averages the rest (``f`` in (0, 0.5), no default), ``median`` is the coordinate-wise median
+    (``train.cohort.robust_delta``); the result takes the server step, a server optimizer or ``--server-scope global``
+    like every other delta.  A cohort of at most 64; rejected with ``--client-dp-clip``.  ``--flip-clients F`` mirrors the
+    training labels of every GPU's virtual clients 0..F-1 (``data.dataset.flip_client_labels``; the hold-out is
+    untouched).  One ``robust`` event in ``--jsonl`` records the aggregate, f, k and F; no CSV and no checkpoint changes.
+    Every rank trims within its own cohort: on W ranks the all-reduce(AVG) yields the mean of W robust estimates, not
+    one estimate over all W * M clients.
 """
 from __future__ import annotations
 
@@ -299,6 +308,56 @@ def cohort_size(cfg: FedAvgConfig) -> int:
     return cfg.cohort if cfg.cohort else cfg.clients_per_gpu
 
 
+def split_aggregate(cfg: FedAvgConfig):
+    """``--aggregate`` names either the clients' weights (mean, weighted, nova: the trainers' ``aggregate``) or a robust
+    estimate (trimmed, median: their ``robust``), which takes no weights.  Returns (the configuration as the checks and
+    events of the weights see it - a robust estimate counts as "mean" there -, the trainers' ``robust``)."""
+    from dataclasses import replace
+    if cfg.aggregate in ("trimmed", "median"):
+        return replace(cfg, aggregate="mean"), cfg.aggregate
+    return cfg, "none"
+
+
+def robust_on(cfg: FedAvgConfig) -> bool:
+    """A robust aggregate or poisoned clients."""
+    return cfg.aggregate in ("trimmed", "median") or cfg.trim_frac != 0 or cfg.flip_clients != 0
+
+
+def check_robust_config(cfg: FedAvgConfig) -> int:
+    """``--aggregate trimmed | median``, ``--trim-frac`` and ``--flip-clients`` act on a cohort round's virtual clients:
+    they need client sampling.  Returns k, the clients dropped at each end (0: not a robust close)."""
+    from .cohort import AGGREGATES, ROBUST_AGGREGATES, ROBUST_MAX_COHORT, trim_count
+    if cfg.aggregate not in AGGREGATES + ROBUST_AGGREGATES:
+        raise ValueError(f"--aggregate must be one of {list(AGGREGATES + ROBUST_AGGREGATES)}, got {cfg.aggregate!r}")
+    if not robust_on(cfg):
+        return 0
+    if cfg.clients_per_gpu <= 1:
+        raise ValueError("--aggregate trimmed / median, --trim-frac and --flip-clients need client sampling "
+                         "(--clients-per-gpu K > 1): they act on a GPU's virtual clients")
+    if cfg.flip_clients < 0 or cfg.flip_clients > cfg.clients_per_gpu:
+        raise ValueError(f"--flip-clients must be in [0, --clients-per-gpu = {cfg.clients_per_gpu}], got "
+                         f"{cfg.flip_clients}")
+    if cfg.trim_frac != 0 and cfg.aggregate != "trimmed":
+        raise ValueError(f"--trim-frac is the share --aggregate trimmed drops at each end: it needs that aggregate, not "
+                         f"--aggregate {cfg.aggregate}")
+    if cfg.aggregate not in ROBUST_AGGREGATES:
+        return 0
+    if cfg.client_dp_clip > 0:
+        raise ValueError(f"--aggregate {cfg.aggregate} does not support --client-dp-clip: the sensitivity of a trimmed "
+                         "mean is not C / M, and no accountant here covers it")
+    M = cohort_size(cfg)
+    if M > ROBUST_MAX_COHORT:
+        raise ValueError(f"--aggregate {cfg.aggregate} needs a cohort of at most {ROBUST_MAX_COHORT} clients, got {M}: "
+                         "the selection kernel holds one parameter's clients in the lanes of one wave")
+    if cfg.aggregate == "trimmed":
+        if cfg.trim_frac == 0:
+            raise ValueError("--aggregate trimmed needs --trim-frac f, the share of the cohort dropped at each end: "
+                             "there is no default")
+        if not 0.0 < cfg.trim_frac < 0.5:
+            raise ValueError(f"--trim-frac must be in (0, 0.5), got {cfg.trim_frac:g}")
+    return trim_count(cfg.aggregate, M, cfg.trim_frac if cfg.aggregate == "trimmed" else None)
+
+
 def check_cohort_config(cfg: FedAvgConfig, backend: str) -> None:
     """Client sampling (--clients-per-gpu K > 1) exists for TinyECG on the fused and torch backends, exact FedAvg."""
     K, M = cfg.clients_per_gpu, cfg.cohort
@@ -381,9 +440,13 @@ def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistCont
     check_client_dp_config(cfg)
     check_server_opt_config(cfg, ctx)
     check_prox_config(cfg, config_name, backend)
-    check_hetero_config(cfg)
+    check_robust_config(cfg)
+    wcfg, robust = split_aggregate(cfg)
+    check_hetero_config(wcfg)
     if cfg.clients_per_gpu > 1:
-        kw = dict(dirichlet_alpha=cfg.client_alpha, local_epochs=cfg.local_epochs, aggregate=cfg.aggregate,
+        kw = dict(robust=robust, trim_frac=cfg.trim_frac if robust == "trimmed" else None,
+                  flip_clients=cfg.flip_clients,
+                  dirichlet_alpha=cfg.client_alpha, local_epochs=cfg.local_epochs, aggregate=wcfg.aggregate,
                   prox_mu=cfg.prox_mu, partition=cfg.client_partition, shards_per_client=cfg.client_shards,
                   clients=cfg.clients_per_gpu, cohort=cohort_size(cfg), lr=cfg.lr, momentum=cfg.momentum, seed=seed,
                   client_dp_clip=cfg.client_dp_clip, client_dp_noise=cfg.client_dp_noise, client_dp_seed=mix64(seed),
@@ -520,7 +583,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         check_prox_config(cfg, cname, pick_backend(cfg, cname, ctx))
     check_client_dp_config(cfg)
     check_server_opt_config(cfg, ctx)
-    check_hetero_config(cfg)
+    robust_k = check_robust_config(cfg)
+    check_hetero_config(split_aggregate(cfg)[0])
     M = cohort_size(cfg)  # clients trained per GPU and round (1: no client sampling)
     all_rows: List[Dict] = []
     fcomm = FedAvgComm(ctx)
@@ -539,6 +603,9 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         if cfg.prox_mu > 0 or cfg.client_partition != "contiguous":
             log.event("prox", config=cname, mu=cfg.prox_mu, partition=cfg.client_partition,
                       shards_per_client=cfg.client_shards)
+        if robust_on(cfg):
+            log.event("robust", config=cname, aggregate=cfg.aggregate, trim_frac=cfg.trim_frac, k=robust_k,
+                      flip_clients=cfg.flip_clients)
         start_round = _resume(cfg, cname, ctx, comm, model, trainer, log) if cfg.resume else 0
         if hasattr(trainer, "set_cohort_round"):  # the cohort sampler is a function of (seed, round): no other state
             trainer.set_cohort_round(start_round)
@@ -562,7 +629,7 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         privacy = []  # DP-SGD: this client's cumulative (round, steps, epsilon)
         cohorts = []  # client sampling: (round, this rank's drawn client ids)
         shapes = []  # unequal clients: (round, this rank's cohort sizes, steps, weights)
-        hetero = hetero_on(cfg) and cfg.clients_per_gpu > 1
+        hetero = hetero_on(split_aggregate(cfg)[0]) and cfg.clients_per_gpu > 1
         client_privacy = []  # client-level DP, rank 0: (round, median client norm, clipped share)
         sample_rate = cfg.batch_size / x.shape[0]
         for r in range(start_round, cfg.rounds):

@@ -28,13 +28,19 @@ struct CohortClose {
   // (nullable) [M] fp32 on the device: Delta = sum_c weight[c] * d_c in place of the mean (cohort_delta_wscale_kernel
   // folds it into scale[], and inv_M is 1); not with a clip norm
   const float* weight;
+  // A robust close (0: none): the coordinate-wise mean of the M - 2 trim middle values of the clients' deltas, 1 <= trim,
+  // 2 trim < M <= 64, with no clip, noise or weight.  Delta goes to ``delta`` or, when the close is not split, to
+  // ``robust_scratch`` [P], from which server_step_kernel takes the step.
+  int trim;
+  float* robust_scratch;
 };
 
 // kOk, or kBadArg for a close that cohort_close must not be given.
 int check_cohort_close(const CohortClose& c);
 
 // The two launches of a checked close: cohort_delta_scale_kernel (``weight`` set: cohort_delta_wscale_kernel), then cohort_delta_kernel (``delta`` set),
-// cohort_server_opt_kernel<opt> (opt != 0) or cohort_dp_mean_kernel.
+// cohort_server_opt_kernel<opt> (opt != 0) or cohort_dp_mean_kernel.  With ``trim`` set there are three: the first as
+// above, cohort_robust_delta_kernel and, unless ``delta`` is set, server_step_kernel<opt>.
 int cohort_close(const CohortClose& c, hipStream_t stream);
 
 }  // namespace tiny

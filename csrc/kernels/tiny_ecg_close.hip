@@ -12,6 +12,14 @@
 //   cohort_delta_kernel        delta = Delta, g left alone                          (the split close)
 // - chosen by cohort_close.  All three form Delta_i with cohort_noise and cohort_delta below, so their bits agree.
 //
+// A robust close (CohortClose::trim k > 0: the coordinate-wise trimmed mean, the median at k = (M - 1) / 2; Yin et al.,
+// "Byzantine-Robust Distributed Learning") is not a linear combination of the deltas and takes three launches:
+// cohort_delta_scale_kernel without a clip (the norms and the round word keep their meaning), then
+//   cohort_robust_delta_kernel  delta = the mean of the M - 2k middle values of d_c[i]  (into the split close's buffer
+//                                                                                        or a [P] scratch)
+// and, unless the close is split, server_step_kernel on (g, scratch) - the kernel the split close's second half runs,
+// so the two ways end on the same bits by construction.
+//
 // The split close exists because a driver of several ranks that wants ONE server optimizer over all their clients must
 // average the deltas first (the adaptive rules are nonlinear in Delta): cohort_delta_kernel ends the round with Delta
 // in a buffer of its own, the caller all-reduces that buffer, and server_step_kernel (ecg_server_opt_step) takes the
@@ -235,6 +243,74 @@ __global__ __launch_bounds__(NT) void server_step_kernel(float* __restrict__ g, 
   m[i] = m1;
 }
 
+// The coordinate-wise trimmed mean of the clients' deltas: with x_c = p_c[i] - g[i] in fp32 (no factor, no weight, no
+// noise), the M values of parameter i are ordered by a 32-bit key - NaN of either sign 0xFFFFFFFF, else the bit
+// pattern with the sign bit flipped (non-negative) or all bits flipped (negative): -inf < ... < -0 < +0 < ... < +inf <
+// NaN - ties by client index, so rank_c = #{j : key_j < key_c or (key_j == key_c and j < c)} is a permutation; client c
+// is kept when trim <= rank_c < M - trim, and
+//   delta[i] = (((x_c1 + x_c2) + ...) + x_cn) * inv_n,    n = M - 2 trim, inv_n = fp32(1 / n),
+// the kept clients in ascending client order, every sum and the product rounded on its own.  The sum starts from -0,
+// the one value with -0 + x == x bit for bit for every x, and takes its terms by a select: no mask is multiplied in.
+//
+// Lanes of a wave are cut into segments of W = 1 << logw >= M lanes (W <= 64); lane (q, c) of a segment holds client
+// c's value of parameter i0 + q, so a wave serves 64 >> logw parameters.  The rank is a loop over j < M that reads lane
+// base + j's key (ds_bpermute); which lanes are kept goes round in one ballot, and the sum is a second loop over j < M
+// that every lane of the segment takes alike, which fixes the order without a reduction tree.  Lanes with c >= M and
+// segments with i >= P load nothing and are read by no live lane (they run the loops, since a cross-lane read needs
+// its source lanes active); lane c == 0 stores.  No LDS, no barrier, no atomics; exactly P floats of a client are read.
+// This file is compiled with -fno-honor-nans -fno-signed-zeros, and here both matter (a NaN client has to sort last, a
+// kept -0 has to stay -0): the body runs under float_control(precise), the NaN test is an integer compare, and a
+// client that is not kept enters the sum as -0 chosen by an integer select - nothing is left for those flags to fold.
+template <int NT>
+__global__ __launch_bounds__(NT) void cohort_robust_delta_kernel(
+    const float* __restrict__ params, const float* __restrict__ global_params, int P, int M, int logw, int trim,
+    float inv_n, float* __restrict__ delta) {
+#pragma float_control(precise, on)
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+  const int i0 = wave << (6 - logw);
+  if (i0 >= P) return;  // wave-uniform
+  const int c = lane & ((1 << logw) - 1), base = lane - c;
+  const int i = i0 + (lane >> logw);
+  const bool live = c < M && i < P;
+  float x = 0.f;
+  uint32_t key = 0u;
+  if (live) {
+    x = params[(long)c * cohort_pstride(P) + i] - global_params[i];
+    const uint32_t b = __float_as_uint(x);
+    key = (b & 0x7FFFFFFFu) > 0x7F800000u ? 0xFFFFFFFFu : ((b & 0x80000000u) ? ~b : (b ^ 0x80000000u));
+  }
+  int rank = 0;
+  for (int j = 0; j < M; ++j) {
+    const uint32_t kj = (uint32_t)__shfl((int)key, base + j, 64);
+    rank += (kj < key || (kj == key && j < c)) ? 1 : 0;
+  }
+  const unsigned long long kept = __ballot(live && rank >= trim && rank < M - trim);
+  float s = -0.f;
+  for (int j = 0; j < M; ++j) {
+    const uint32_t xj = (uint32_t)__shfl((int)__float_as_uint(x), base + j, 64);
+    s = s + __uint_as_float(((kept >> (base + j)) & 1ull) ? xj : 0x80000000u);
+  }
+  if (live && c == 0) delta[i] = s * inv_n;
+}
+
+// server_step_kernel<256, opt> on ``n`` floats (opt 0..4, checked by the caller; ``step`` is the step size itself).
+void launch_server_step(float* g, const float* delta, long n, int opt, float step, float b1, float b2, float tau,
+                        float* m, float* v, hipStream_t stream) {
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+#define ECG_SERVER_STEP_LAUNCH(OPT) \
+  hipLaunchKernelGGL((server_step_kernel<256, OPT>), grid, block, 0, stream, g, delta, n, step, b1, b2, tau, m, v)
+  switch (opt) {
+    case 0: ECG_SERVER_STEP_LAUNCH(0); break;
+    case SOPT_SGDM: ECG_SERVER_STEP_LAUNCH(SOPT_SGDM); break;
+    case SOPT_ADAGRAD: ECG_SERVER_STEP_LAUNCH(SOPT_ADAGRAD); break;
+    case SOPT_ADAM: ECG_SERVER_STEP_LAUNCH(SOPT_ADAM); break;
+    default: ECG_SERVER_STEP_LAUNCH(SOPT_YOGI); break;
+  }
+#undef ECG_SERVER_STEP_LAUNCH
+}
+
 int check_server_opt(int opt, float b1, float b2, float tau, const float* m, const float* v) {
   if (opt < SOPT_SGDM || opt > SOPT_YOGI || !m) return ecg::kBadArg;
   if (!(b1 >= 0.f && b1 < 1.f) || !(b2 >= 0.f && b2 < 1.f)) return ecg::kBadArg;
@@ -250,6 +326,11 @@ int ecg::tiny::check_cohort_close(const CohortClose& c) {
   if (c.clip < 0.f || c.sigma < 0.f || c.server_lr < 0.f || (c.sigma > 0.f && c.clip == 0.f)) return ecg::kBadArg;
   // the sensitivity of a weighted, clipped mean is not C / M, and no accountant here covers it
   if (c.weight && c.clip > 0.f) return ecg::kBadArg;
+  // a robust close: 1 <= trim and 2 trim < M, a cohort that fits a wave, nothing that scales or perturbs a delta (the
+  // sensitivity of a trimmed mean is not C / M), and somewhere to put Delta
+  if (c.trim != 0 && (c.trim < 0 || 2 * c.trim >= c.M || c.M > 64 || c.clip > 0.f || c.sigma > 0.f || c.weight ||
+                      (!c.robust_scratch && !c.delta)))
+    return ecg::kBadArg;
   if (c.delta) return ecg::kOk;  // the split close reads neither the optimizer nor its state
   return c.opt != 0 ? check_server_opt(c.opt, c.beta1, c.beta2, c.tau, c.m, c.v) : ecg::kOk;
 }
@@ -273,6 +354,20 @@ int ecg::tiny::cohort_close(const CohortClose& c, hipStream_t stream) {
                        (const float*)c.global, c.P, c.M, c.clip > 0.f ? c.clip : FLT_MAX, c.scale, c.norm,
                        c.round_word);
   ECG_HIP_CHECK(hipGetLastError());
+  if (c.trim != 0) {  // the robust close: the selection, then (not split) the split close's own second half
+    int logw = 0;
+    while ((1 << logw) < c.M) ++logw;
+    const int per_block = 4 * (64 >> logw);
+    float* out = c.delta ? c.delta : c.robust_scratch;
+    hipLaunchKernelGGL(cohort_robust_delta_kernel<256>, dim3((c.P + per_block - 1) / per_block), dim3(256), 0, stream,
+                       c.params, (const float*)c.global, c.P, c.M, logw, c.trim, 1.0f / (float)(c.M - 2 * c.trim), out);
+    ECG_HIP_CHECK(hipGetLastError());
+    if (!c.delta) {
+      launch_server_step(c.global, out, (long)c.P, c.opt, eta, c.beta1, c.beta2, c.tau, c.m, c.v, stream);
+      ECG_HIP_CHECK(hipGetLastError());
+    }
+    return ecg::kOk;
+  }
   const dim3 grid((c.P + 255) / 256), block(256);
 #define ECG_SERVER_OPT_LAUNCH(OPT)                                                                                 \
   hipLaunchKernelGGL((cohort_server_opt_kernel<256, OPT>), grid, block, 0, stream, c.params, c.global, c.P, c.M, inv_M, \
@@ -359,6 +454,19 @@ ECG_API int ecg_cohort_weighted_close(const float* params, float* global, int nc
                           v, delta, weight}, stream);
 }
 
+// ecg_cohort_weighted_close's twin for the robust close: ``trim`` k (1 <= k, 2 k < M <= 64) clients are dropped at each
+// end of every parameter's order and the rest averaged (cohort_robust_delta_kernel; no clip, no weight, no noise), then
+// the plain step (``opt`` 0), a server optimizer (1..4) on ``scratch`` [P], or, with ``delta`` non-null, the split
+// close (``global`` is only read and ``scratch`` may be null).  ``scale`` receives ones, ``norm`` the delta norms.
+ECG_API int ecg_cohort_robust_close(const float* params, float* global, int nc, int M, int trim, float server_lr,
+                                    unsigned long long* round_word, float* scale, float* norm, int opt, float b1,
+                                    float b2, float tau, float* m, float* v, float* delta, float* scratch,
+                                    hipStream_t stream) {
+  if (trim < 1) return ecg::kBadArg;  // (that is ecg_cohort_dp_close and its twins)
+  return close_entry(nc, {params, global, 0, M, 0.f, 0.f, server_lr, 0ull, round_word, scale, norm, opt, b1, b2, tau, m,
+                          v, delta, nullptr, trim, scratch}, stream);
+}
+
 // One server step on ``g`` [n] from ``delta`` [n] (the second half of the split close, after the caller averaged the
 // ranks' deltas): ``opt`` 0 the plain step g += eta delta (m and v are not read and may be null), 1 sgdm, 2 adagrad, 3
 // adam, 4 yogi with the server state ``m`` / ``v`` [n], read and written (``v`` may be null for sgdm); eta == 0 means
@@ -371,18 +479,7 @@ ECG_API int ecg_server_opt_step(float* g, const float* delta, long n, int opt, f
     if (st) return st;
   }
   if ((n + 255) / 256 > (long)INT_MAX) return ecg::kTooLarge;
-  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  const float step = eta == 0.f ? 1.f : eta;
-#define ECG_SERVER_STEP_LAUNCH(OPT) \
-  hipLaunchKernelGGL((server_step_kernel<256, OPT>), grid, block, 0, stream, g, delta, n, step, b1, b2, tau, m, v)
-  switch (opt) {
-    case 0: ECG_SERVER_STEP_LAUNCH(0); break;
-    case SOPT_SGDM: ECG_SERVER_STEP_LAUNCH(SOPT_SGDM); break;
-    case SOPT_ADAGRAD: ECG_SERVER_STEP_LAUNCH(SOPT_ADAGRAD); break;
-    case SOPT_ADAM: ECG_SERVER_STEP_LAUNCH(SOPT_ADAM); break;
-    default: ECG_SERVER_STEP_LAUNCH(SOPT_YOGI); break;
-  }
-#undef ECG_SERVER_STEP_LAUNCH
+  launch_server_step(g, delta, n, opt, eta == 0.f ? 1.f : eta, b1, b2, tau, m, v, stream);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }

@@ -2270,7 +2270,7 @@ ECG_API int ecg_tiny_cohort_wprep_stride(void) { return kCohortWprepStride; }
 // rows gathered by the previous reduce - and need wprep, xg, yg and xbg, sized for M * B rows
 // (ecg_tiny_gather_floats / _halfs(L, M * B)); fp32 rounds take none of them.  There is no DP-SGD in a cohort.
 // The close: with the cdp_* fields, server_lr, server_opt and server_delta all zero (server_lr 1 counts as zero) it is
-// cohort_mean_kernel; anything else - client_weight among it - is ecg::tiny::cohort_close (include/tiny_ecg_close.h), which picks its kernel by
+// cohort_mean_kernel; anything else - client_weight and robust_trim among it - is ecg::tiny::cohort_close (include/tiny_ecg_close.h), which picks its kernel by
 // server_delta, then server_opt.
 // ops/_lib.py mirrors this struct (TinyCohortRound) and checks its size against ecg_tiny_cohort_round_sizeof().
 struct EcgTinyCohortRound {
@@ -2328,6 +2328,13 @@ struct EcgTinyCohortRound {
   // close is always ecg::tiny::cohort_close with these weights (CohortClose::weight), never cohort_mean_kernel.  It
   // needs cdp_scale, cdp_norm and cdp_round and cdp_clip == 0.  Read when a round runs, like client_steps.
   const float* client_weight;
+  // A robust close (robust_trim k != 0): the coordinate-wise trimmed mean of the clients' deltas, k dropped at each end
+  // (CohortClose::trim; the median at k = (M - 1) / 2), through ecg::tiny::cohort_close.  It needs 1 <= k, 2 k < M <=
+  // 64, cdp_scale, cdp_norm and cdp_round, no clip, noise or client_weight, and ``robust_scratch`` [P] unless
+  // server_delta is set.  A scalar baked into a captured graph: a trainer's M and k are fixed.  Both zero: the
+  // launches of before.
+  int robust_trim;
+  float* robust_scratch;
 };
 
 ECG_API int ecg_tiny_cohort_round_sizeof(void) { return (int)sizeof(EcgTinyCohortRound); }
@@ -2338,12 +2345,17 @@ static bool cohort_dp_on(const EcgTinyCohortRound& r) {
   return r.cdp_clip > 0.f || (r.server_lr != 0.f && r.server_lr != 1.f) || r.server_opt != 0;
 }
 
+// The round ends on ecg::tiny::cohort_close, not on cohort_mean_kernel.
+static bool cohort_close_on(const EcgTinyCohortRound& r) {
+  return cohort_dp_on(r) || r.server_delta || r.client_weight || r.robust_trim != 0;
+}
+
 // The round's close as ecg::tiny::cohort_close takes it.
 static CohortClose cohort_close_args(const EcgTinyCohortRound& r) {
   return {r.params,   r.global_params, make_layout(r.nc).P, r.M,           r.cdp_clip,    r.cdp_sigma,
           r.server_lr, r.cdp_seed,     r.cdp_round,         r.cdp_scale,   r.cdp_norm,    r.server_opt,
           r.server_beta1, r.server_beta2, r.server_tau,     r.server_m,    r.server_v,    r.server_delta,
-          r.client_weight};
+          r.client_weight, r.robust_trim, r.robust_scratch};
 }
 
 static int check_cohort_round(const EcgTinyCohortRound* r) {
@@ -2359,7 +2371,7 @@ static int check_cohort_round(const EcgTinyCohortRound* r) {
   const long rows = (long)r->M * r->B;
   if (rows * r->slab_stride * 4 > INT_MAX || rows * (pack_ldb(r->L) + 8) * 4 > INT_MAX) return ecg::kTooLarge;
   if (r->prox_mu < 0.f) return ecg::kBadArg;
-  if (cohort_dp_on(*r) || r->server_delta || r->client_weight) return check_cohort_close(cohort_close_args(*r));
+  if (cohort_close_on(*r)) return check_cohort_close(cohort_close_args(*r));
   // the plain mean reads none of the close's fields; a negative clip norm, or noise without a clip norm, is an error
   return (r->cdp_clip < 0.f || r->cdp_sigma != 0.f) ? ecg::kBadArg : ecg::kOk;
 }
@@ -2391,7 +2403,7 @@ static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream)
                                 r.client_steps, s);
     if (st) return st;
   }
-  if (cohort_dp_on(r) || r.server_delta || r.client_weight) return cohort_close(cohort_close_args(r), stream);
+  if (cohort_close_on(r)) return cohort_close(cohort_close_args(r), stream);
   hipLaunchKernelGGL(cohort_mean_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, r.params, r.global_params,
                      P, r.M, 1.0f / (float)r.M);
   ECG_HIP_CHECK(hipGetLastError());

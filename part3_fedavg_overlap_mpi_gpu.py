@@ -34,6 +34,10 @@ runs of the GPU's label-sorted training windows - label-skewed, non-IID clients 
 virtual clients of unequal sizes by the label-Dirichlet split, min(local steps, E passes over its own windows) local
 steps per client, and the cohort's deltas averaged with n_k / n or with FedNova's normalised weights; not with
 --client-dp-clip, nova not with --prox-mu)
+--aggregate {trimmed,median} --trim-frac f --flip-clients F (need --clients-per-gpu: robust aggregation - per parameter
+the floor(f * M) smallest and largest of the cohort's M <= 64 deltas are dropped and the rest averaged, f in (0, 0.5)
+without a default, or the coordinate-wise median; F > 0 mirrors the training labels of virtual clients 0..F-1, the
+poisoned clients to be robust against; not with --client-dp-clip)
 """
 from __future__ import annotations
 
