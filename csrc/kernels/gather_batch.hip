@@ -25,9 +25,13 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_rows_kernel(const 
   TO* dst = out + (long)b * ldo;
   float mean = 0.f, inv = 1.f;
   if (normalize) {
+    // mean = x0 + mean(x - x0): a constant window (a flat-line lead) has mean exactly x0, so it normalizes to exactly
+    // 0; the fp32 mean of the raw values misses a constant c by an ulp for most c and L, and (c - mean) / (|c - mean|
+    // + eps) is then +-0.9 in every sample
+    const float x0 = src[0];
     float s = 0.f;
-    for (int i = lane; i < L; i += 64) s += src[i];
-    mean = ecg::wave_sum(s) / (float)L;
+    for (int i = lane; i < L; i += 64) s += src[i] - x0;
+    mean = x0 + ecg::wave_sum(s) / (float)L;
     float v = 0.f;
     for (int i = lane; i < L; i += 64) {
       float d = src[i] - mean;

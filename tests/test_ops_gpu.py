@@ -168,3 +168,98 @@ def test_conv1d_flag_call_matches_torch(B, K):
         ref = F.conv1d(x.unsqueeze(1), w.view(1, 1, K))[:, 0]
         torch.testing.assert_close(y, ref, rtol=1e-5, atol=1e-4)
         del junk
+
+
+# n = 1, 3: only the scalar tail loop; 1459: float4 body + a 3-element tail; 2_097_155: the capped grid (2048 blocks x
+# 256 threads x 4 floats = 2_097_152 elements in one sweep) plus a 3-element tail
+@pytest.mark.parametrize("inv_scale", [1.0, 0.5])
+@pytest.mark.parametrize("momentum,wd,nesterov", [(0.9, 1e-3, False), (0.9, 0.0, True)])
+@pytest.mark.parametrize("n", [1, 3, 1459, 2_097_155])
+def test_flat_sgd_tail_elements(n, momentum, wd, nesterov, inv_scale):
+    """Three steps of sgd_flat_kernel on buffers whose length is no multiple of 4 (the scalar tail loop) against
+    torch.optim.SGD in float64; with inv_scale = 0.5 and a finite gradient the update uses g * inv_scale and found_inf
+    stays 0."""
+    from crossscale_ecg.ops.sgd import FlatSGD
+    gen = torch.Generator(device=DEV).manual_seed(n)
+    p = torch.randn(n, device=DEV, generator=gen)
+    g = torch.zeros_like(p)
+    fi = torch.zeros(1, dtype=torch.int32, device=DEV) if inv_scale != 1.0 else None
+    opt = FlatSGD(p, g, lr=0.05, momentum=momentum, weight_decay=wd, nesterov=nesterov)
+    q = torch.nn.Parameter(p.double().clone())
+    ref = torch.optim.SGD([q], lr=0.05, momentum=momentum, weight_decay=wd, nesterov=nesterov)
+    for _ in range(3):
+        g.copy_(torch.randn(n, device=DEV, generator=gen))
+        opt.step(inv_scale=inv_scale, found_inf=fi)
+        q.grad = g.double() * inv_scale
+        ref.step()
+    torch.cuda.synchronize()
+    assert fi is None or fi.item() == 0
+    assert torch.allclose(p.double(), q.detach(), rtol=1e-5, atol=1e-6), (p.double() - q.detach()).abs().max().item()
+    assert torch.allclose(opt.buf.double(), ref.state[q]["momentum_buffer"], rtol=1e-5, atol=1e-6)
+
+
+def _gather_ref(rows, normalize):
+    ref = rows.double()
+    if normalize:
+        ref = (ref - ref.mean(1, keepdim=True)) / (ref.std(1, unbiased=False, keepdim=True) + 1e-8)
+    return ref
+
+
+def _gather_check(x, idx, B, normalize):
+    """gather_rows (fp32 and bf16 outputs) against float64 at test_gather_rows's tolerances."""
+    from crossscale_ecg.ops.gather import gather_rows
+    rows = x[idx.long()] if idx is not None else x[:B]
+    ref = _gather_ref(rows, normalize)
+    out = gather_rows(x, idx, batch=B, normalize=normalize)
+    outb = gather_rows(x, idx, batch=B, normalize=normalize, dtype=torch.bfloat16)
+    torch.cuda.synchronize()
+    assert out.shape == (B, x.shape[1]) and torch.isfinite(out).all()
+    assert torch.allclose(out.double(), ref, atol=1e-5, rtol=1e-5), (out.double() - ref).abs().max().item()
+    assert torch.allclose(outb.double(), ref, atol=3e-2 * max(1, ref.abs().max().item()), rtol=1e-2)
+    return out, outb
+
+
+@pytest.mark.parametrize("normalize", [False, True])
+@pytest.mark.parametrize("B", [1, 5])
+@pytest.mark.parametrize("L", [1, 63, 333, 502])
+def test_gather_rows_short_and_odd_rows(L, B, normalize):
+    """Rows shorter than a wave (L = 1, 63), odd (333) and with L % 4 != 0 (502: no 16-byte path); fewer rows than the
+    four waves of a block, and one row past them."""
+    torch.manual_seed(L + B)
+    x = torch.randn(37, L, device=DEV) * 3 + 1
+    idx = torch.randperm(37, device=DEV)[:B].int()
+    _gather_check(x, idx, B, normalize)
+
+
+@pytest.mark.parametrize("normalize", [False, True])
+@pytest.mark.parametrize("L,lo", [(500, 4), (500, 1), (333, 3)])
+def test_gather_rows_strided_and_misaligned_source(L, lo, normalize):
+    """The source is a column slice of a wider tensor whose other columns hold 1e30 (ldx > L: a read past the row's
+    L values shows at once); lo = 4 keeps the slice 16-byte aligned on every fourth row only, lo = 1 (x[:, 1:]) starts
+    it 4 bytes past a 16-byte boundary with L % 4 == 0, where only the alignment test keeps the kernel off its
+    16-byte loads.  With and without an index (idx=None gathers rows 0 .. B-1)."""
+    torch.manual_seed(L + lo)
+    wide = torch.full((40, lo + L + (0 if lo == 1 else 7)), 1e30, device=DEV)
+    wide[:, lo:lo + L] = torch.randn(40, L, device=DEV) * 3 + 1
+    x = wide[:, lo:lo + L]
+    assert x.stride(0) > L or lo == 1
+    idx = torch.randperm(40, device=DEV)[:9].int()
+    _gather_check(x, idx, 9, normalize)
+    _gather_check(x, None, 6, normalize)
+    _gather_check(x, None, 40, normalize)  # batch omitted == every row
+    from crossscale_ecg.ops.gather import gather_rows
+    assert torch.equal(gather_rows(x, None, normalize=normalize), gather_rows(x, None, batch=40, normalize=normalize))
+
+
+@pytest.mark.parametrize("L", [63, 333, 500, 502])
+@pytest.mark.parametrize("c", [1.7, 0.1, -0.37, 3.0])
+def test_gather_rows_constant_row_normalizes_to_zero(L, c):
+    """A constant window (a flat-line lead) has variance 0: its z-score is exactly 0, finite, in fp32 and bf16 - also
+    for values whose fp32 sum over L samples is not exact (1.7, 0.1, -0.37), next to ordinary rows that stay within
+    the float64 tolerance."""
+    torch.manual_seed(L)
+    x = torch.randn(8, L, device=DEV) * 3 + 1
+    x[2] = c
+    idx = torch.tensor([5, 2, 0], dtype=torch.int32, device=DEV)
+    out, outb = _gather_check(x, idx, 3, True)
+    assert torch.all(out[1] == 0) and torch.all(outb[1] == 0)

@@ -16,14 +16,14 @@ def _rel(a, b):
     return (a.float() - b.float()).norm().item() / (b.float().norm().item() + 1e-12)
 
 
-def _setup(depth=18, B=32, L=500, seed=0, **kw):
+def _setup(depth=18, B=32, L=500, seed=0, ncls=2, **kw):
     from crossscale_ecg.models.resnet1d import resnet1d18, resnet1d34
     from crossscale_ecg.ops.resnet_engine import ResNetStepEngine
     torch.manual_seed(seed)
-    m = (resnet1d18 if depth == 18 else resnet1d34)().to(DEV)
+    m = (resnet1d18 if depth == 18 else resnet1d34)(num_classes=ncls).to(DEV)
     ref = copy.deepcopy(m)
     x = torch.randn(B, 1, L, device=DEV)
-    y = torch.randint(0, 2, (B,), device=DEV)
+    y = torch.randint(0, ncls, (B,), device=DEV)
     eng = ResNetStepEngine(m, B, L, **kw)
     eng.set_batch(x, y)
     return m, ref, eng, x, y
@@ -267,15 +267,14 @@ def _g(eng, p):
     return eng.grad[off:off + p.numel()].view_as(p).double()
 
 
-@pytest.mark.parametrize("depth", [18, 34])
-def test_engine_teacher_forced_numerics(depth):
+def _teacher_forced(depth, B, L, ncls, seed=0):
     """Every op of the engine pinned against float64, teacher-forced: each block's forward recomputed from the
     engine's own input activation, each block's backward from the engine's own incoming gradient and saved
     activations (models/resnet1d_ref.py, itself checked against autograd in test_resnet_ref_cpu.py); the head
     and the stem likewise.  Per-tensor relative error bounds: forward 1 %, every parameter gradient and every
-    propagated input gradient 2 % (measured worst: 0.42 % at depth 18, 0.37 % at depth 34)."""
+    propagated input gradient 2 %, loss 1e-3.  Returns {tensor: relative error}."""
     from crossscale_ecg.models.resnet1d_ref import block_backward_reference, block_forward_reference, bn_apply
-    m, ref, eng, x, y = _setup(depth, B=32, use_graph=False)
+    m, ref, eng, x, y = _setup(depth, B=B, L=L, seed=seed, ncls=ncls, use_graph=False)
     eps = m.bn1.eps
     W = lambda w: w.detach().to(torch.bfloat16).double()  # noqa: E731  (the engine's MFMA weight operands)
     pbn = lambda b: (b.weight.detach().double(), b.bias.detach().double())  # noqa: E731
@@ -352,7 +351,16 @@ def test_engine_teacher_forced_numerics(depth):
     dW0 = torch.nn.grad.conv1d_weight(x64, m.conv1.weight.shape, zl.grad, 2, 3)
     check("stem.conv1.weight", _g(eng, m.conv1.weight), dW0, 0.02)
     top = sorted(worst.items(), key=lambda kv: -kv[1])[:8]
-    print(f"depth {depth}: worst per-tensor relative errors", [(k, round(v, 5)) for k, v in top])
+    print(f"depth {depth} B {B} L {L} ncls {ncls}: worst per-tensor relative errors",
+          [(k, round(v, 5)) for k, v in top])
+    return worst
+
+
+@pytest.mark.parametrize("depth", [18, 34])
+def test_engine_teacher_forced_numerics(depth):
+    """The teacher-forced per-op pin (_teacher_forced) at the benchmark shape (measured worst: 0.42 % at depth 18,
+    0.37 % at depth 34)."""
+    _teacher_forced(depth, 32, 500, 2)
 
 
 def test_engine_bn_tail_matches_separate_finalize(monkeypatch):
@@ -423,3 +431,103 @@ def test_pre_activation_bitwise_equals_bn_act_pass(monkeypatch):
     assert torch.equal(f0, f1) and torch.equal(m0, m1)
     assert all(torch.equal(a, b) for a, b in zip(b0, b1))
     assert n1 == n0 - 16  # one BN_ACT per block
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Off the benchmark shape.  Everything above runs at L = 500 (lengths 250 / 125 / 125, 63, 32, 16: even stem output,
+# unclipped last pool window), 2 classes and B in {16, 32, 64, 640, 1024}.  (B, L, ncls, depth) below, with the
+# lengths Lz / Lp / stages each one gives:
+OFF_SHAPES = [
+    (5, 250, 2, 18),    # 125 / 63 / 63, 32, 16, 8: odd Lz - the last pool window is clipped
+    (3, 333, 5, 18),    # 167 / 84 / 84, 42, 21, 11: odd L and Lz, stride 2 from an odd length (21 -> 11), 5 classes
+    (3, 64, 2, 18),     # 32 / 16 / 16, 8, 4, 2: a few rows per stage (layer4: 6), one BatchNorm partial row above the
+                        # stem, the fused tail's one-group path
+    (7, 37, 16, 18),    # 19 / 10 / 10, 5, 3, 2: 16 classes (the head's MAXC), odd everything, L % 4 != 0
+    (1, 500, 2, 18),    # B = 1: 1 / B in the head, three empty row groups in the head reduce
+    (33, 100, 3, 18),   # 50 / 25 / 25, 13, 7, 4: B no multiple of the 32 row lanes or the 4 reduce groups
+    (200, 64, 5, 18),   # Gb = 3: head-reduce slices of 66 / 67 / 67 samples
+    (4, 2000, 2, 18),   # 1000 / 500 / 500, 250, 125, 63: B * Lz far above the later stages (stem_chunk, maxel)
+    (5, 16, 2, 18),     # 8 / 4 / 4, 2, 1, 1: stage length 1 - both outer taps masked on every row, a stride-2 conv
+                        # on one input row, the head at Lf = 1
+    (3, 333, 5, 34),    # the odd chain through 16 blocks
+]
+
+
+@pytest.mark.parametrize("B,L,ncls,depth", OFF_SHAPES)
+def test_engine_teacher_forced_off_shapes(B, L, ncls, depth):
+    """The teacher-forced per-op pin at window lengths, batch sizes and class counts away from the benchmark's, with
+    the bounds of the benchmark shape: forward 1 %, gradients 2 %, loss 1e-3."""
+    _teacher_forced(depth, B, L, ncls)
+
+
+PLAN_SHAPES = [(3, 64, 2), (33, 333, 5)]  # one partial row per BatchNorm / a handful; odd lengths and ragged tiles
+
+
+@pytest.mark.parametrize("B,L,ncls", PLAN_SHAPES)
+def test_engine_graph_equals_eager_bitwise_off_shapes(B, L, ncls, monkeypatch):
+    monkeypatch.setenv("ECG_RESNET_SIDE", "0")
+    m, ref, eng, x, y = _setup(18, B=B, L=L, ncls=ncls, use_graph=False)
+    assert not eng.side_lane
+    eng.forward_backward()
+    g_eager = eng.grad.clone()
+    eng.use_graph = True
+    eng.forward_backward()
+    torch.cuda.synchronize()
+    assert torch.equal(eng.grad, g_eager)
+
+
+@pytest.mark.parametrize("B,L,ncls", PLAN_SHAPES)
+def test_engine_bn_tail_matches_separate_finalize_off_shapes(B, L, ncls, monkeypatch):
+    """Fused BatchNorm finalize == the separate BN_FIN ops where a BatchNorm has one partial row or a handful: the
+    tail's level 1 is a single group (gs = 8 >= T)."""
+    from crossscale_ecg.ops.resnet_engine import ResNetStepEngine
+    monkeypatch.setenv("ECG_BN_TAIL", "1")
+    m, ref, eng, x, y = _setup(18, B=B, L=L, ncls=ncls, use_graph=True)
+    monkeypatch.setenv("ECG_BN_TAIL", "0")
+    eng0 = ResNetStepEngine(ref, B, L, use_graph=True)
+    eng0.set_batch(x, y)
+    assert eng.bn_tail and not eng0.bn_tail and eng.n_bn_tails > 0
+    assert eng0.n_ops > eng.n_ops + eng.n_bn_tails - 1
+    for _ in range(3):  # the counters are reset by every launch's final reducers
+        eng.forward_backward()
+        eng0.forward_backward()
+    torch.cuda.synchronize()
+    assert torch.isfinite(eng.grad).all()
+    assert _rel(eng.grad, eng0.grad) < 1e-5
+    for (n, b), (_, b0) in zip(m.named_buffers(), ref.named_buffers()):
+        if b.is_floating_point():
+            assert _rel(b, b0) < 1e-5, n
+
+
+@pytest.mark.parametrize("B,L,ncls", PLAN_SHAPES)
+def test_pre_activation_bitwise_equals_bn_act_pass_off_shapes(B, L, ncls, monkeypatch):
+    """The pre-activation fold == the BN_ACT pass, bit for bit, over two SGD steps; one plan op fewer for every block
+    whose second conv takes the fold at this shape."""
+    outs = []
+    for mode in ("0", "1"):
+        monkeypatch.setenv("ECG_RESNET_PREACT", mode)
+        m, ref, eng, x, y = _setup(18, B=B, L=L, ncls=ncls, seed=5)
+        assert eng.pre_act == (mode == "1")
+        folded = sum(bool(eng.lib.ecg_conv1d_nlc_pa_ok(B, Lo, Co, Lo, Co, 3, 1, 1, 1)) for _, _, Lo, Co, _ in eng._shapes)
+        eng.step()
+        eng.step()
+        torch.cuda.synchronize()
+        outs.append((eng.flat.clone(), eng.mom.clone(), [b.clone() for b in m.buffers()], eng.n_ops))
+        del eng, m, ref
+    (f0, m0, b0, n0), (f1, m1, b1, n1) = outs
+    assert torch.isfinite(f0).all()
+    assert torch.equal(f0, f1) and torch.equal(m0, m1)
+    assert all(torch.equal(a, b) for a, b in zip(b0, b1))
+    assert folded > 0 and n1 == n0 - folded
+
+
+@pytest.mark.parametrize("B,L,ncls", PLAN_SHAPES)
+def test_engine_forward_backward_deterministic_off_shapes(B, L, ncls):
+    """Two forward_backward() calls on one batch give the same gradient bits (every reduction has a fixed order)."""
+    m, ref, eng, x, y = _setup(18, B=B, L=L, ncls=ncls)
+    eng.forward_backward()
+    g = eng.grad.clone()
+    eng.forward_backward()
+    torch.cuda.synchronize()
+    assert torch.isfinite(g).all() and g.abs().max().item() > 0
+    assert torch.equal(eng.grad, g)
