@@ -45,6 +45,8 @@ def _bind(lib):
     _lib._sig(lib, "ecg_conv1d_nlc_fwd_stat_rows", [i32] * 9)
     _lib._sig(lib, "ecg_conv1d_nlc_fwd_pa", [vp] * 7 + [i32] * 10 + [vp, vp, vp, vp])
     _lib._sig(lib, "ecg_conv1d_nlc_pa_ok", [i32] * 9)
+    _lib._sig(lib, "ecg_conv1d_nlc_fwd_kernel_id", [i32] * 10)
+    _lib._sig(lib, "ecg_conv1d_nlc_wgrad_kernel_id", [i32] * 9)
     lib._conv_mc_bound = True
 
 
@@ -100,6 +102,91 @@ def stat_rows(B: int, L_in: int, c_in: int, L_out: int, c_out: int, k: int = 3, 
     multi-tile, one-tile - and its tile size depend on the whole shape, not just M and c_out)."""
     return _lib_k().ecg_conv1d_nlc_fwd_stat_rows(int(B), int(L_in), int(c_in), int(L_out), int(c_out), int(k),
                                                  int(stride), int(pad), int(in_dil))
+
+
+_FWD_LOOPS = {1: "tap64", 2: "tap", 3: "dgrad_s2", 4: "dma", 5: "dma_mt", 6: "reg"}
+_WGRAD_LOOPS = {1: "ts", 2: "dma2", 3: "dma", 4: "reg"}
+
+
+def fwd_kernel(B: int, L_in: int, c_in: int, L_out: int, c_out: int, k: int = 3, stride: int = 1, pad: int = 1,
+               in_dil: int = 1, stats: bool = False) -> str:
+    """Name of the kernel the forward / data-grad entry point runs for that exact conv under the current toggles:
+    ``tap64`` (persistent 64-channel tap kernel), ``tap128`` / ``tap64c`` (tap-shared 256-row kernel, 128 / 64 columns),
+    ``dgrad_s2_128`` / ``dgrad_s2_64`` (tap-shared strided data-grad), or the one-tap ``dma_BMxBN`` (LDS-DMA loop, one
+    tile per workgroup), ``dma_mt_BMxBN`` (its multi-tile form), ``reg_BMxBN`` (register-staged loop); ``none`` when no
+    kernel takes the call.  ``stats``: whether the call writes BatchNorm partial rows."""
+    v = _lib_k().ecg_conv1d_nlc_fwd_kernel_id(int(B), int(L_in), int(c_in), int(L_out), int(c_out), int(k), int(stride),
+                                              int(pad), int(in_dil), int(bool(stats)))
+    loop, bm, bn = v // 1000000, v // 1000 % 1000, v % 1000
+    if loop == 0:
+        return "none"
+    if loop == 1:
+        return "tap64"
+    if loop == 2:
+        return "tap128" if bn == 128 else "tap64c"
+    if loop == 3:
+        return f"dgrad_s2_{bn}"
+    return f"{_FWD_LOOPS[loop]}_{bm}x{bn}"
+
+
+def wgrad_kernel(splits: int, B: int, L_in: int, c_in: int, L_out: int, c_out: int, k: int = 3, stride: int = 1,
+                 pad: int = 1) -> str:
+    """Name of the weight-gradient kernel for that conv and split count under the current toggles: ``ts`` (tap-shared),
+    ``dma2`` (two-group LDS-DMA, 128x128), ``dma_256x256`` (LDS-DMA), ``reg_BMxBN`` (register-staged, C_out rows x
+    tap*C_in columns); ``none`` for arguments the entry point rejects."""
+    v = _lib_k().ecg_conv1d_nlc_wgrad_kernel_id(int(splits), int(B), int(L_in), int(c_in), int(L_out), int(c_out),
+                                                int(k), int(stride), int(pad))
+    loop, bm, bn = v // 1000000, v // 1000 % 1000, v % 1000
+    if loop == 0:
+        return "none"
+    if loop in (1, 2):
+        return _WGRAD_LOOPS[loop]
+    return f"{_WGRAD_LOOPS[loop]}_{bm}x{bn}"
+
+
+def wgrad_default_splits(B: int, L_in: int, c_in: int, L_out: int, c_out: int, k: int, stride: int, pad: int) -> int:
+    """The split count ``wgrad_raw`` plans when none is given."""
+    lib = _lib_k()
+    splits = lib.ecg_conv1d_nlc_wgrad_splits(B, L_in, c_in, L_out, c_out, k, stride, pad)
+    if not splits:  # target workgroups, >= 8 chunks each, <= 256 slices
+        chunks = (B * L_out + 63) // 64
+        tiles = lib.ecg_conv1d_nlc_wgrad_tiles(c_out, k, c_in)
+        target = lib.ecg_conv1d_nlc_wgrad_target_wgs(c_out, k, c_in, B, L_in, L_out)
+        splits = max(1, min(256, max(1, chunks // 8), max(1, target // max(1, tiles))))
+    return splits
+
+
+def fwd_ex_raw(x: torch.Tensor, w_t: torch.Tensor, stride: int, pad: int, L_out: int, in_dil: int = 1,
+               bias: Optional[torch.Tensor] = None, add: Optional[torch.Tensor] = None,
+               add_mask: Optional[torch.Tensor] = None, relu: int = 0, bnb=None, stats: bool = False,
+               check: bool = True):
+    """The forward / data-grad entry point with its whole epilogue argument set (tests).  ``relu``: bit 0 = ReLU on
+    the output, bit 1 = ``bnb[0]`` is the mask as bits.  ``bnb``: None or the nine operands {smask, sz, smean, srstd,
+    szd, smean_d, srstd_d, mscale, mshift} (tensors or None) of the BatchNorm-backward mode.  ``stats`` (implied by
+    ``bnb``): allocate and return the partial rows [2 or 3, stat_rows, Cout] fp32.  Returns (status, y, stats);
+    ``check`` raises on a non-zero status."""
+    B, Lin, Cin = x.shape
+    Cout, K, _ = w_t.shape
+    for t in (x, w_t, add, add_mask):
+        if t is not None and not (t.dtype == torch.bfloat16 and t.is_contiguous()):
+            raise ValueError("fwd_ex_raw: contiguous bf16 x, w_t, add, add_mask required")
+    if bias is not None and not (bias.dtype == torch.float32 and bias.is_contiguous()):
+        raise ValueError("fwd_ex_raw: contiguous fp32 bias required")
+    if bnb is not None and (len(bnb) != 9 or any(t is not None and not t.is_contiguous() for t in bnb)):
+        raise ValueError("fwd_ex_raw: bnb is nine contiguous tensors or None")
+    y = torch.empty((B, L_out, Cout), dtype=torch.bfloat16, device=x.device)
+    st_t = None
+    if stats or bnb is not None:
+        rows = stat_rows(B, Lin, Cin, L_out, Cout, K, stride, pad, in_dil)
+        st_t = torch.zeros((3 if bnb is not None and bnb[4] is not None else 2, rows, Cout), dtype=torch.float32,
+                           device=x.device)
+    arr = None if bnb is None else (_lib.C.c_void_p * 9)(*[_lib.ptr(t) for t in bnb])
+    st = _lib_k().ecg_conv1d_nlc_fwd_ex(x.data_ptr(), w_t.data_ptr(), _lib.ptr(bias), y.data_ptr(), _lib.ptr(st_t),
+                                        _lib.ptr(add), _lib.ptr(add_mask), B, Lin, Cin, L_out, Cout, K, stride, pad,
+                                        in_dil, int(relu), arr, None, _lib.stream_ptr(x.device))
+    if check:
+        _lib.check(st, "ecg_conv1d_nlc_fwd_ex")
+    return st, y, st_t
 
 
 def fwd_stats_raw(x: torch.Tensor, w_t: torch.Tensor, stride: int, pad: int, L_out: int):
@@ -166,25 +253,25 @@ def fwd_raw(x: torch.Tensor, w_t: torch.Tensor, bias: Optional[torch.Tensor], st
     return y
 
 
-def wgrad_raw(dy: torch.Tensor, x: torch.Tensor, K: int, stride: int, pad: int,
-              splits: Optional[int] = None) -> torch.Tensor:
-    """dw [Cout, K, Cin] fp32 from dy [B, Lout, Cout] and x [B, Lin, Cin] (bf16)."""
+def wgrad_parts_raw(dy: torch.Tensor, x: torch.Tensor, K: int, stride: int, pad: int,
+                    splits: Optional[int] = None) -> torch.Tensor:
+    """Split-K partials [splits, Cout, K * Cin] fp32 of the weight gradient from dy [B, Lout, Cout] and x [B, Lin, Cin]
+    (bf16); their sum over dim 0 is dw."""
     B, Lout, Cout = dy.shape
     _, Lin, Cin = x.shape
-    R = B * Lout
-    chunks = (R + 63) // 64
-    lib = _lib_k()
-    tiles = lib.ecg_conv1d_nlc_wgrad_tiles(Cout, K, Cin)
-    if splits is None:  # the tap-shared kernel's plan, else: target workgroups, >= 8 chunks each, <= 256 slices
-        splits = lib.ecg_conv1d_nlc_wgrad_splits(B, Lin, Cin, Lout, Cout, K, stride, pad)
-    if not splits:
-        target = lib.ecg_conv1d_nlc_wgrad_target_wgs(Cout, K, Cin, B, Lin, Lout)
-        splits = max(1, min(256, max(1, chunks // 8), max(1, target // max(1, tiles))))
+    if not splits:  # the tap-shared kernel's plan, else: target workgroups, >= 8 chunks each, <= 256 slices
+        splits = wgrad_default_splits(B, Lin, Cin, Lout, Cout, K, stride, pad)
     part = torch.empty((splits, Cout, K * Cin), dtype=torch.float32, device=dy.device)
     st = _lib_k().ecg_conv1d_nlc_wgrad(dy.data_ptr(), x.data_ptr(), part.data_ptr(), splits, B, Lin, Cin, Lout, Cout, K,
                                        stride, pad, _lib.stream_ptr(dy.device))
     _lib.check(st, "ecg_conv1d_nlc_wgrad")
-    return part.sum(0).view(Cout, K, Cin)
+    return part
+
+
+def wgrad_raw(dy: torch.Tensor, x: torch.Tensor, K: int, stride: int, pad: int,
+              splits: Optional[int] = None) -> torch.Tensor:
+    """dw [Cout, K, Cin] fp32 from dy [B, Lout, Cout] and x [B, Lin, Cin] (bf16)."""
+    return wgrad_parts_raw(dy, x, K, stride, pad, splits).sum(0).view(dy.shape[2], K, x.shape[2])
 
 
 class Conv1dNLC(torch.autograd.Function):

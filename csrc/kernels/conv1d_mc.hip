@@ -1567,15 +1567,6 @@ int launch_fwd_dma_mt(const FwdArgs& a, int GM, hipStream_t stream) {
   return ecg::kOk;
 }
 
-template <int BM, int BN, int EPI>
-int launch_fwd_dma(const FwdArgs& a, hipStream_t stream) {
-  if constexpr (BM == 128 && BN == 64) {
-    const int GM = fwd_mt_groups((long)a.B * a.Lout, a.Cout, a.in_dil, BM, BN);
-    if (GM > 0) return launch_fwd_dma_mt<BM, BN, EPI>(a, GM, stream);
-  }
-  return launch_fwd_dma_st<BM, BN, EPI>(a, stream);
-}
-
 // Register-staged loop: the fallback for operands beyond the LDS-DMA loop's 32-bit buffer offsets (and, with
 // ecg_conv1d_nlc_set_dma_dil(0), the strided data-grads - a test cross-check).
 template <int BM, int BN, int EPI>
@@ -1609,20 +1600,57 @@ int launch_fwd_cfg(const FwdArgs& a, hipStream_t stream) {
 int g_conv_dma_dil = 1;
 inline bool conv_dma_dil() { return g_conv_dma_dil == 1; }
 
-template <int BM, int BN>
-int launch_fwd(const FwdArgs& a, hipStream_t stream) {
+// The kernel that runs a forward / data-grad call, chosen in one place (pick_fwd) from the whole shape: the launch
+// switches on it and ecg_conv1d_nlc_fwd_kernel_id reports it.
+enum FwdLoop {
+  kFwdNone = 0,     // no kernel takes the call (kBadArg)
+  kFwdTap64 = 1,    // persistent 64-channel tap kernel (128-row tiles)
+  kFwdTap = 2,      // tap-shared 256-row kernel, 128 or 64 columns
+  kFwdDgradS2 = 3,  // tap-shared strided data-grad (128 i-rows), 128 or 64 columns
+  kFwdDmaSt = 4,    // one-tap bm x bn, LDS-DMA loop, one tile per workgroup
+  kFwdDmaMt = 5,    // one-tap bm x bn, LDS-DMA loop, multi-tile workgroups (gm along M)
+  kFwdReg = 6,      // one-tap bm x bn, register-staged loop
+};
+struct FwdPick {
+  int loop, bm, bn, gm;
+};
+inline int fwd_pick_id(const FwdPick& p) { return p.loop * 1000000 + p.bm * 1000 + p.bn; }
+
+// ``stats``: the call writes BatchNorm partial rows (the host sized them for the multi-tile kernel where that one is
+// the DMA choice, so the register-staged fallback cannot stand in for it).
+inline FwdPick pick_fwd(int B, int Lin, int Cin, int Lout, int Cout, int Kw, int stride, int pad, int in_dil,
+                        bool stats) {
+  if (tap64_ok(B, Lin, Cin, Lout, Cout, Kw, stride, pad, in_dil)) return {kFwdTap64, T64_BM, 64, 0};
+  if (conv_tap(Cout) && tap_ok(B, Lin, Cin, Lout, Cout, Kw, stride, pad, in_dil))
+    return {kFwdTap, TAP_BM, Cout % 128 == 0 ? 128 : 64, 0};
+  if (tap_s2_ok(B, Lin, Cin, Lout, Cout, Kw, stride, pad, in_dil))
+    return {kFwdDgradS2, S2_IR, Cout % 128 == 0 ? 128 : 64, 0};
+  const long M = (long)B * Lout;
+  int bm, bn;
+  pick_fwd_tile(M, Cout, in_dil, &bm, &bn);
   // the DMA loop addresses bytes with 32-bit buffer offsets from the tile's first sample
-  const int Lrow = a.in_dil > 1 ? (a.Lout + a.in_dil - 1) / a.in_dil : a.Lout;
-  const bool dma_ok = (a.in_dil == 1 || (conv_dma_dil() && a.stride == 1 && BM <= 128)) &&
-                      (long)(BM / Lrow + 2) * a.Lin * a.Cin * 2 < 0x7fff0000L &&
-                      (long)a.Cout * a.Kw * a.Cin * 2 < 0x7fff0000L;
-  if (dma_ok && a.in_dil > 1)  // two stages, one tile per workgroup
-    return a.stat_mode == 1 ? launch_fwd_dma_st<BM, BN, 1>(a, stream) : launch_fwd_dma_st<BM, BN, 0>(a, stream);
-  if (dma_ok) return a.stat_mode == 1 ? launch_fwd_dma<BM, BN, 1>(a, stream) : launch_fwd_dma<BM, BN, 0>(a, stream);
-  if (a.stats && fwd_mt_groups((long)a.B * a.Lout, a.Cout, a.in_dil, BM, BN) > 0)
-    return ecg::kBadArg;  // the host sized the partial rows for the multi-tile kernel
-  if constexpr (BM > 128) return ecg::kBadArg;  // 256-row tiles exist only as DMA kernels (the picker ensures it)
-  else return a.stat_mode == 1 ? launch_fwd_cfg<BM, BN, 1>(a, stream) : launch_fwd_cfg<BM, BN, 0>(a, stream);
+  const int Lrow = in_dil > 1 ? (Lout + in_dil - 1) / in_dil : Lout;
+  const bool dma_ok = (in_dil == 1 || (conv_dma_dil() && stride == 1 && bm <= 128)) &&
+                      (long)(bm / Lrow + 2) * Lin * Cin * 2 < 0x7fff0000L && (long)Cout * Kw * Cin * 2 < 0x7fff0000L;
+  const int gm = fwd_mt_groups(M, Cout, in_dil, bm, bn);  // > 0 only for 128x64 tiles of undilated calls
+  if (dma_ok) return {gm > 0 ? kFwdDmaMt : kFwdDmaSt, bm, bn, gm};  // (dilated: two stages, one tile per workgroup)
+  if (stats && gm > 0) return {kFwdNone, bm, bn, 0};  // the host sized the partial rows for the multi-tile kernel
+  if (bm > 128) return {kFwdNone, bm, bn, 0};  // 256-row tiles exist only as DMA kernels (the picker ensures it)
+  return {kFwdReg, bm, bn, 0};
+}
+
+template <int BM, int BN>
+int launch_fwd(const FwdArgs& a, const FwdPick& p, hipStream_t stream) {
+  const bool b = a.stat_mode == 1;
+  if (p.loop == kFwdDmaSt) return b ? launch_fwd_dma_st<BM, BN, 1>(a, stream) : launch_fwd_dma_st<BM, BN, 0>(a, stream);
+  if (p.loop == kFwdDmaMt) {
+    if constexpr (BM == 128 && BN == 64)
+      return b ? launch_fwd_dma_mt<BM, BN, 1>(a, p.gm, stream) : launch_fwd_dma_mt<BM, BN, 0>(a, p.gm, stream);
+    else
+      return ecg::kBadArg;
+  }
+  if constexpr (BM > 128) return ecg::kBadArg;
+  else return b ? launch_fwd_cfg<BM, BN, 1>(a, stream) : launch_fwd_cfg<BM, BN, 0>(a, stream);
 }
 
 // ------------------------------------------------------------------------------------------- weight grad
@@ -2435,16 +2463,34 @@ ECG_API int ecg_conv1d_nlc_fwd_pa(const void* x, const void* w, const float* bia
     return tap64_ok(B, Lin, Cin, Lout, Cout, Kw, stride, pad, in_dil) ? launch_tap64(a, stream)
                                                                       : launch_fwd_tap(a, stream);
   }
-  if (tap64_ok(B, Lin, Cin, Lout, Cout, Kw, stride, pad, in_dil)) return launch_tap64(a, stream);
-  if (conv_tap(Cout) && tap_ok(B, Lin, Cin, Lout, Cout, Kw, stride, pad, in_dil)) return launch_fwd_tap(a, stream);
-  if (tap_s2_ok(B, Lin, Cin, Lout, Cout, Kw, stride, pad, in_dil)) return launch_dgrad_s2(a, stream);
-  int bm, bn;
-  pick_fwd_tile((long)B * Lout, Cout, in_dil, &bm, &bn);
-  if (bm == 256 && bn == 256) return launch_fwd<256, 256>(a, stream);
-  if (bm == 256) return launch_fwd<256, 128>(a, stream);
-  if (bm == 128 && bn == 128) return launch_fwd<128, 128>(a, stream);
-  if (bm == 128) return launch_fwd<128, 64>(a, stream);
-  return launch_fwd<64, 64>(a, stream);
+  const FwdPick p = pick_fwd(B, Lin, Cin, Lout, Cout, Kw, stride, pad, in_dil, stats != nullptr);
+  switch (p.loop) {
+    case kFwdTap64: return launch_tap64(a, stream);
+    case kFwdTap: return launch_fwd_tap(a, stream);
+    case kFwdDgradS2: return launch_dgrad_s2(a, stream);
+    case kFwdDmaSt:
+    case kFwdDmaMt:
+    case kFwdReg:
+      if (p.bm == 256 && p.bn == 256) return launch_fwd<256, 256>(a, p, stream);
+      if (p.bm == 256) return launch_fwd<256, 128>(a, p, stream);
+      if (p.bm == 128 && p.bn == 128) return launch_fwd<128, 128>(a, p, stream);
+      if (p.bm == 128) return launch_fwd<128, 64>(a, p, stream);
+      return launch_fwd<64, 64>(a, p, stream);
+    default: return ecg::kBadArg;
+  }
+}
+
+// The kernel ecg_conv1d_nlc_fwd_pa runs for this conv under the current toggles, as FwdLoop * 1000000 + rows * 1000 +
+// columns of its tile (FwdLoop: 1 persistent 64-channel tap, 2 tap-shared, 3 tap-shared strided data-grad, one-tap on
+// 4 the LDS-DMA loop with one tile per workgroup, 5 its multi-tile form, 6 the register-staged loop); 0: none
+// (kBadArg).  ``stats``: whether the call writes BatchNorm partial rows.
+ECG_API int ecg_conv1d_nlc_fwd_kernel_id(int B, int Lin, int Cin, int Lout, int Cout, int Kw, int stride, int pad,
+                                         int in_dil, int stats) {
+  if (B <= 0 || Lin <= 0 || Lout <= 0 || Kw <= 0 || stride <= 0 || in_dil <= 0 || pad < 0 || Cin % BK != 0 ||
+      Cout % 64 != 0)
+    return 0;
+  const FwdPick p = pick_fwd(B, Lin, Cin, Lout, Cout, Kw, stride, pad, in_dil, stats != 0);
+  return p.loop == kFwdNone ? 0 : fwd_pick_id(p);
 }
 
 // Persistent 64-channel tap kernel on (1) / off (0); returns the previous setting (tests, A/B).  Step plans size
@@ -2534,6 +2580,25 @@ inline bool wgrad_dma_ok(long cps, int Lin, int Cin, int Lout, int Cout) {
   return rows * Cout * 2 < 0x7fff0000L && (rows / Lout + 2) * (long)Lin * Cin * 2 < 0x7fff0000L;
 }
 
+// The weight-gradient kernel of a call, chosen in one place: the launch switches on it and
+// ecg_conv1d_nlc_wgrad_kernel_id reports it.  ``splits`` matters: the LDS-DMA loops need the rows of one split within
+// their 32-bit offsets.
+enum WgLoop { kWgNone = 0, kWgTs = 1, kWgDma2 = 2, kWgDma = 3, kWgReg = 4 };
+struct WgPick {
+  int loop, bm, bn;
+};
+inline WgPick pick_wgrad(int splits, int B, int Lin, int Cin, int Lout, int Cout, int Kw, int stride, int pad) {
+  if (wgrad_ts_ok(B, Lin, Cin, Lout, Cout, Kw, stride, pad)) return {kWgTs, 64, 64};
+  const long R = (long)B * Lout;
+  const int nchunks = (int)((R + 63) / 64);
+  const int cps = (nchunks + splits - 1) / splits;
+  const bool bm128 = Cout % 128 == 0, bn128 = Cin % 128 == 0;
+  const bool dma_ok = wgrad_dma_ok(cps, Lin, Cin, Lout, Cout);
+  if (wgrad_big(Cout, Cin)) return {dma_ok ? kWgDma : kWgReg, 256, 256};
+  if (bm128 && bn128 && dma_ok) return {kWgDma2, 128, 128};
+  return {kWgReg, bm128 ? 128 : 64, bn128 ? 128 : 64};
+}
+
 // Partial weight gradients: part[splits][Cout][Kw*Cin] fp32 (sum over dim 0 = dw in [Cout][Kw][Cin]).
 // ``splits`` workgroup slices of the (b,t) reduction; returns kBadArg unless Cin, Cout % 64 == 0.
 ECG_API int ecg_conv1d_nlc_wgrad(const void* dy, const void* x, float* part, int splits, int B, int Lin, int Cin,
@@ -2545,16 +2610,30 @@ ECG_API int ecg_conv1d_nlc_wgrad(const void* dy, const void* x, float* part, int
   const int cps = (nchunks + splits - 1) / splits;
   WgradArgs a{static_cast<const __bf16*>(dy), static_cast<const __bf16*>(x), part, B, Lin, Cin, Lout, Cout, Kw,
               stride, pad, cps, make_fastdiv(Lout)};
-  if (wgrad_ts_ok(B, Lin, Cin, Lout, Cout, Kw, stride, pad)) return launch_wgrad_ts(a, splits, stream);
-  const bool bm128 = Cout % 128 == 0, bn128 = Cin % 128 == 0;
-  const bool dma_ok = wgrad_dma_ok(cps, Lin, Cin, Lout, Cout);
-  if (wgrad_big(Cout, Cin)) return dma_ok ? launch_wgrad_dma<256, 256>(a, splits, stream)
-                                          : launch_wgrad<256, 256>(a, splits, stream);
-  if (bm128 && bn128 && dma_ok) return launch_wgrad_dma2(a, splits, stream);
-  if (bm128 && bn128) return launch_wgrad<128, 128>(a, splits, stream);
-  if (bm128) return launch_wgrad<128, 64>(a, splits, stream);
-  if (bn128) return launch_wgrad<64, 128>(a, splits, stream);
+  const WgPick p = pick_wgrad(splits, B, Lin, Cin, Lout, Cout, Kw, stride, pad);
+  switch (p.loop) {
+    case kWgTs: return launch_wgrad_ts(a, splits, stream);
+    case kWgDma2: return launch_wgrad_dma2(a, splits, stream);
+    case kWgDma: return launch_wgrad_dma<256, 256>(a, splits, stream);
+    default: break;
+  }
+  if (p.bm == 256) return launch_wgrad<256, 256>(a, splits, stream);
+  if (p.bm == 128 && p.bn == 128) return launch_wgrad<128, 128>(a, splits, stream);
+  if (p.bm == 128) return launch_wgrad<128, 64>(a, splits, stream);
+  if (p.bn == 128) return launch_wgrad<64, 128>(a, splits, stream);
   return launch_wgrad<64, 64>(a, splits, stream);
+}
+
+// The kernel ecg_conv1d_nlc_wgrad runs for this conv and split count under the current toggles, as WgLoop * 1000000 +
+// C_out rows * 1000 + tap*C_in columns of its tile (WgLoop: 1 tap-shared, 2 two-group LDS-DMA, 3 LDS-DMA 256x256,
+// 4 register-staged); 0: none (kBadArg).
+ECG_API int ecg_conv1d_nlc_wgrad_kernel_id(int splits, int B, int Lin, int Cin, int Lout, int Cout, int Kw, int stride,
+                                           int pad) {
+  if (splits <= 0 || B <= 0 || Lin <= 0 || Lout <= 0 || Kw <= 0 || stride <= 0 || pad < 0 || Cin % 64 != 0 ||
+      Cout % 64 != 0)
+    return 0;
+  const WgPick p = pick_wgrad(splits, B, Lin, Cin, Lout, Cout, Kw, stride, pad);
+  return p.loop * 1000000 + p.bm * 1000 + p.bn;
 }
 
 // Workgroup tiles (C_out tiles x tap*C_in tiles) the weight-gradient kernel uses for this shape (split sizing).
