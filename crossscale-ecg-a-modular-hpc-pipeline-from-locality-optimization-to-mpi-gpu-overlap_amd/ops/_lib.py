@@ -84,7 +84,8 @@ class TinyCohortRound(C.Structure):
                 ("cdp_norm", vp), ("cdp_round", vp), ("server_opt", i32), ("server_beta1", f32), ("server_beta2", f32),
                 ("server_tau", f32), ("server_m", vp), ("server_v", vp), ("server_delta", vp),
                 ("prox_mu", f32), ("client_steps", vp), ("client_weight", vp),
-                ("robust_trim", i32), ("robust_scratch", vp)]
+                ("robust_trim", i32), ("robust_scratch", vp),
+                ("dp_clip", f32), ("dp_sigma", f32), ("dp_seed", u64), ("dp_scale", vp), ("dp_step", vp)]
 
 
 def _bind_kernels(lib: C.CDLL) -> None:
@@ -106,6 +107,9 @@ def _bind_kernels(lib: C.CDLL) -> None:
                                                   vp])
     _sig(lib, "ecg_slab_reduce_cohort_steps_sgd", [vp, i32, i32, i32, i32, vp, vp, vp, f32, f32, f32, i32, vp, vp, f32,
                                                    vp, i32, vp])
+    _sig(lib, "ecg_slab_reduce_cohort_dp_sgd", [vp, i32, i32, i32, i32, vp, vp, vp, f32, f32, f32, i32, vp, vp, f32,
+                                                vp, i32, f32, f32, u64, vp, vp, vp])
+    _sig(lib, "ecg_dp_noise_stream", [vp, i32, u64, u64, C.c_uint, vp])
     native = _sig(lib, "ecg_tiny_round_sizeof", [])()
     if native != C.sizeof(TinyRound):
         raise NativeError(f"EcgTinyRound is {native} bytes in libecg_kernels.so but {C.sizeof(TinyRound)} in "

@@ -7,7 +7,15 @@ The fused step kernel runs one workgroup per window, so a client with a small ba
 cohort's ``cohort * B`` windows and ONE reduce + SGD launch over its clients, then the clients' mean in ascending
 cohort order into the global weights - captured into one hipGraph like a single client's round.  Virtual clients keep
 no state between rounds (weights from the global model, zero momentum), and which clients and rows a round uses is a
-pure function of ``(seed, round)`` (``data.dataset.CohortSampler``).  Limit: no DP-SGD in a cohort.
+pure function of ``(seed, round)`` (``data.dataset.CohortSampler``).
+
+Record-level DP-SGD (``dp_clip`` C > 0, ``dp_noise`` sigma; not with FedProx): every client's every local step clips
+its B per-sample gradients to l2 norm C and adds noise of standard deviation ``sigma * C / B`` per parameter - per step
+``dp_row_scale_cohort_kernel`` over the cohort's ``M * B`` slab rows and ``slab_reduce_cohort_dp_sgd_kernel`` (its
+STEPS form with unequal local work) in place of the plain cohort reduce, whichever close the round has.  Cohort slot c
+draws ``philox.normal(dp_seed, t, P, stream=2 + c)`` (``dp_seed`` has no default: ``dp_clip`` > 0 without it is an error), t the 64-bit step word this trainer owns on the device
+(``dp_step``; host mirror ``dp_steps``, ``set_dp_steps`` on resume), advanced once per cohort step whichever clients
+are frozen (``train/cohort.py`` states the definition).
 
 Client-level DP (``client_dp_clip`` > 0; DP-FedAvg) and a server step size ``server_lr`` != 1 close the round with
 ``cohort_delta_scale_kernel`` + ``cohort_dp_mean_kernel`` in place of the mean: every client's round delta clipped to
@@ -64,7 +72,7 @@ from ..data.dataset import CohortSampler, client_partition, flipped_labels
 from ..models.tiny_ecg import TinyECG, num_params
 from .fused_tiny import _check_dataset, labels_int32, prec_id, slab_stride
 from .tiny_eval import EvalResult, TinyEvaluator, tiny_evaluate
-from ..train.cohort import (check_aggregate, check_client_dp, check_robust, client_dp_seed_of,
+from ..train.cohort import (check_aggregate, check_client_dp, check_cohort_dp, check_robust, client_dp_seed_of,
                             client_dp_sigma_share, cohort_round_shape, load_server_state, trim_count)
 from ..train.server_opt import BETA1, BETA2, TAU, check_server_opt, check_server_scope, server_opt_init
 
@@ -77,7 +85,7 @@ class FusedCohortTrainer:
                  steps_per_round: int, clients: int, cohort: Optional[int] = None, lr: float = 1e-2,
                  momentum: float = 0.9, weight_decay: float = 0.0, nesterov: bool = False, seed: Optional[int] = None,
                  use_graph: Optional[bool] = None, precision: str = "bf16", dp_clip: float = 0.0,
-                 client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
+                 dp_noise: float = 0.0, dp_seed: Optional[int] = None, client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
                  server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
                  server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank",
                  prox_mu: float = 0.0, partition: str = "contiguous", shards_per_client: int = 2,
@@ -89,9 +97,7 @@ class FusedCohortTrainer:
         check_robust(robust, aggregate, client_dp_clip)
         self.robust = robust
         self.trim = trim_count(robust, clients if not cohort else int(cohort), trim_frac)  # 0: not a robust close
-        if dp_clip > 0.0:
-            raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients: the cohort "
-                             "reduce has no per-sample clip")
+        check_cohort_dp(dp_clip, dp_noise, dp_seed, prox_mu)  # (fp16 is no precision of the fused kernels: prec_id)
         check_client_dp(client_dp_clip, client_dp_noise, server_lr, world_size)
         self.server_opt_id = check_server_opt(server_opt, server_beta1, server_beta2, server_tau)
         self.server_scope = check_server_scope(server_scope)
@@ -183,6 +189,15 @@ class FusedCohortTrainer:
             self.cdp_scale = torch.ones(self.M, **f32)
             self.cdp_norm = torch.zeros(self.M, **f32)
             self.cdp_round = torch.zeros(1, dtype=torch.int64, device=self.device)
+        # record-level DP-SGD: the cohort's clip factors (scratch) and the step word every step's noise is drawn from
+        self.dp_clip, self.dp_noise = float(dp_clip), float(dp_noise)
+        self.dp = self.dp_clip > 0.0
+        self.dp_seed = (0 if dp_seed is None else int(dp_seed)) & (2 ** 64 - 1)  # (None: DP-SGD is off)
+        self.dp_steps = 0  # host mirror of dp_step: the t of the next cohort step's noise
+        self.dp_scale = self.dp_step = None
+        if self.dp:
+            self.dp_scale = torch.zeros(rows, **f32)
+            self.dp_step = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._round = _lib.TinyCohortRound(
             X=self.x.data_ptr(), ldx=self.x.stride(0), Y=self.y32.data_ptr(), params=self.cparams.data_ptr(),
             mom=self.cmom.data_ptr(), slab=self.slab.data_ptr(), loss_acc=self.loss_acc.data_ptr(),
@@ -190,7 +205,11 @@ class FusedCohortTrainer:
             global_params=self.params.data_ptr(), L=L, nc=self.nc, slab_stride=self.stride, B=self.B, M=self.M,
             fanout=1, lr=self.lr, momentum=self.momentum, wd=self.wd, nesterov=int(self.nesterov), prec=self.prec,
             prox_mu=self.prox_mu)
-        if self.client_dp:  # (all-zero fields otherwise: the round then issues the launches it always issued)
+        if self.dp:  # (all-zero fields otherwise, here and below: the launches the round always issued)
+            r = self._round
+            r.dp_clip, r.dp_sigma, r.dp_seed = self.dp_clip, self.dp_noise, self.dp_seed
+            r.dp_scale, r.dp_step = self.dp_scale.data_ptr(), self.dp_step.data_ptr()
+        if self.client_dp:
             r = self._round
             r.cdp_clip, r.cdp_sigma = self.cdp_clip, client_dp_sigma_share(self.cdp_noise, world_size)
             r.server_lr, r.cdp_seed = self.server_lr, self.cdp_seed
@@ -241,7 +260,7 @@ class FusedCohortTrainer:
     def prepare(self, sizes) -> None:
         """Capture, upload and warm every round graph whose step count is in ``sizes`` (on both index tables).  The
         warm-up replays are rolled back: global weights, loss words, tables and the round counter - the device word of
-        the DP close and the server optimizer's m / v with it - stay as found (the per-client buffers are scratch that
+        the DP close, the DP-SGD step word and the server optimizer's m / v with it - stay as found (the per-client buffers are scratch that
         every round's fan-out rewrites; so is ``server_delta`` of scope "global", whose graphs write neither the
         weights nor m / v: no step has to be replayed or undone)."""
         if not self.use_graph:
@@ -252,7 +271,7 @@ class FusedCohortTrainer:
         state += tuple(t for pair in self._pairs.values() for t in pair)
         if self.client_dp:
             state += (self.cdp_round, self.cdp_scale, self.cdp_norm)
-        state += tuple(t for t in (self.server_m, self.server_v) if t is not None)
+        state += tuple(t for t in (self.server_m, self.server_v, self.dp_step) if t is not None)
         snap = [t.clone() for t in state]
         stream = _lib.stream_ptr(self.device)
         for n in sizes:
@@ -278,6 +297,12 @@ class FusedCohortTrainer:
         self.cohort_round = int(r)
         if self.cdp_round is not None:
             self.cdp_round.fill_(int(r))
+
+    def set_dp_steps(self, n: int) -> None:
+        """Continue the record-level noise at cohort step ``n`` (checkpoint resume)."""
+        self.dp_steps = int(n)
+        if self.dp_step is not None:
+            self.dp_step.fill_(int(n))
 
     def server_state(self) -> Dict[str, torch.Tensor]:
         """The server optimizer's state (copies on the CPU): ``server_m`` and, for the adaptive rules, ``server_v``;
@@ -330,6 +355,8 @@ class FusedCohortTrainer:
         self._shape = self._staged_shape
         self.cohort_round += 1
         self.steps_done += n
+        if self.dp:
+            self.dp_steps += n
         self._loss_steps += n
         self._loss_samples += self.B * (sum(self._shape[1]) if self.hetero else self.M * n)
         return self.idx_table

@@ -49,6 +49,14 @@ parameter's clients in the lanes of one wave); "median" with M <= 2 has k == 0 a
 its own cohort: W ranks end on the mean of W robust estimates, not on one estimate over all W * M clients.
 ``flip_clients`` F > 0 (``data.dataset.flip_client_labels``): the training labels of clients 0..F-1 are mirrored - the
 poisoned clients a robust aggregate is there for.
+
+Record-level DP-SGD inside the cohort (``dp_clip`` C > 0, ``dp_noise`` sigma; not with FedProx, fp16 AMP or DDP): local
+step s of cohort slot j is ``TorchLocalTrainer``'s DP step - per-sample gradients from ``torch.func``, each clipped in
+fp32 to l2 norm C, summed, plus ``sigma * C * z``, divided by B, then the optimizer's update - with ``z =
+philox.normal(dp_seed, t0 + s, P, stream=2 + j)``: stream 2 + j keeps the M clients of one step independent (0 is the
+single client's DP-SGD, 1 the client-level close), and ``t0`` is ``dp_steps`` at the round's start, which every round
+advances by its ``n`` whichever clients run fewer steps (``set_dp_steps`` on resume).  The close is whichever the other
+arguments name; ``dp_seed`` has no default (``dp_clip`` > 0 without it is an error); ``dp_row_scale_cohort_kernel`` and ``slab_reduce_cohort_dp_sgd_kernel`` implement the step.
 """
 from __future__ import annotations
 
@@ -72,7 +80,7 @@ class TorchCohortTrainer:
                  steps_per_round: int, clients: int, cohort: Optional[int] = None, lr: float = 1e-2,
                  momentum: float = 0.9, weight_decay: float = 0.0, nesterov: bool = False,
                  amp_dtype: Optional[torch.dtype] = None, seed: Optional[int] = None, dp_clip: float = 0.0,
-                 client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
+                 dp_noise: float = 0.0, dp_seed: Optional[int] = None, client_dp_clip: float = 0.0, client_dp_noise: float = 0.0, client_dp_seed: Optional[int] = None,
                  server_lr: float = 1.0, world_size: int = 1, server_opt: str = "none", server_beta1: float = BETA1,
                  server_beta2: float = BETA2, server_tau: float = TAU, server_scope: str = "rank",
                  prox_mu: float = 0.0, partition: str = "contiguous", shards_per_client: int = 2,
@@ -84,8 +92,11 @@ class TorchCohortTrainer:
         self.robust = robust
         self.trim = trim_count(robust, clients if not cohort else int(cohort), trim_frac)
         self.prox_mu = float(prox_mu)
-        if dp_clip > 0.0:
-            raise ValueError("DP-SGD (dp_clip > 0) is not implemented for cohorts of virtual clients")
+        check_cohort_dp(dp_clip, dp_noise, dp_seed, prox_mu, amp_dtype, model)
+        self.dp_clip, self.dp_noise = float(dp_clip), float(dp_noise)
+        self.dp = self.dp_clip > 0.0
+        self.dp_seed = (0 if dp_seed is None else int(dp_seed)) & philox.MASK64  # (None: DP-SGD is off)
+        self.dp_steps = 0  # the t of the next cohort step's noise
         check_client_dp(client_dp_clip, client_dp_noise, server_lr, world_size)
         check_server_opt(server_opt, server_beta1, server_beta2, server_tau)
         self.server_scope = check_server_scope(server_scope)
@@ -137,6 +148,39 @@ class TorchCohortTrainer:
     def set_cohort_round(self, r: int) -> None:
         self.cohort_round = int(r)
 
+    def set_dp_steps(self, n: int) -> None:
+        """Continue the record-level noise at cohort step ``n`` (checkpoint resume)."""
+        self.dp_steps = int(n)
+
+    def _dp_step(self, opt, j: int, t: int, xb: torch.Tensor, yb: torch.Tensor, use_amp: bool) -> torch.Tensor:
+        """One DP-SGD step of cohort slot j on the work model (the module docstring's definition); the batch's mean
+        loss."""
+        from torch.func import functional_call, grad, vmap
+        names = [n for n, _ in self.work.named_parameters()]
+        params = {n: p.detach() for n, p in self.work.named_parameters()}
+
+        def sample_loss(p, x1, y1):
+            with torch.autocast(device_type=self.device.type, dtype=self.amp_dtype or torch.float32, enabled=use_amp):
+                loss = F.cross_entropy(functional_call(self.work, p, (x1.unsqueeze(0),)), y1.unsqueeze(0))
+            return loss, loss.detach()
+
+        grads, losses = vmap(grad(sample_loss, has_aux=True), in_dims=(None, 0, 0))(params, xb, yb)
+        B = xb.shape[0]
+        g = torch.cat([grads[n].reshape(B, -1).float() for n in names], dim=1)  # [B, P]
+        norms = g.norm(dim=1)
+        c = torch.where(norms > 0, (self.dp_clip / norms).clamp(max=1.0), torch.ones_like(norms))
+        total = (g * c[:, None]).sum(0)
+        if self.dp_noise > 0.0:
+            z = philox.normal(self.dp_seed, t, g.shape[1], stream=2 + j)
+            total = total + (self.dp_noise * self.dp_clip) * torch.from_numpy(z).to(total)
+        total = total / B
+        off = 0
+        for p in self.work.parameters():
+            p.grad = total[off:off + p.numel()].view_as(p).to(p.dtype)
+            off += p.numel()
+        opt.step()
+        return losses.float().mean()
+
     def server_state(self) -> Dict[str, torch.Tensor]:
         """The server optimizer's state (copies on the CPU): ``server_m`` and, for the adaptive rules, ``server_v``."""
         return {k: t.detach().cpu().clone() for k, t in (("server_m", self.server_m), ("server_v", self.server_v))
@@ -157,6 +201,9 @@ class TorchCohortTrainer:
             sel = table[s, j * self.B:(j + 1) * self.B].long()
             xb, yb = self.x[sel].unsqueeze(1), self.y[sel]
             opt.zero_grad(set_to_none=True)
+            if self.dp:
+                self.loss_acc += self._dp_step(opt, j, self.dp_steps + s, xb, yb, use_amp)
+                continue
             with torch.autocast(device_type=self.device.type, dtype=self.amp_dtype or torch.float32, enabled=use_amp):
                 loss = F.cross_entropy(self.work(xb), yb)
             loss.backward()
@@ -194,6 +241,8 @@ class TorchCohortTrainer:
                 for pg, t in zip(self.model.parameters(), total):
                     pg.copy_(t * inv)
         self.steps_done += n
+        if self.dp:
+            self.dp_steps += n
         self._loss_steps += n
         self._loss_client_steps += sum(steps)
 
@@ -456,6 +505,29 @@ def check_client_dp(clip: float, noise: float, server_lr: float, world_size: int
         raise ValueError("server_lr must be > 0")
     if world_size < 1:
         raise ValueError("world_size must be >= 1")
+
+
+def check_cohort_dp(dp_clip: float, dp_noise: float, dp_seed: Optional[int], prox_mu: float = 0.0, amp_dtype=None,
+                    model=None) -> None:
+    """Record-level DP-SGD inside a cohort: the single client's rules (``TorchLocalTrainer``), and the noise key has
+    no default - ``dp_clip`` > 0 without ``dp_seed`` stays the error it was before the cohort trainers took DP-SGD."""
+    if not dp_clip >= 0.0 or not dp_noise >= 0.0:
+        raise ValueError(f"dp_clip and dp_noise must be >= 0, got {dp_clip} and {dp_noise}")
+    if dp_noise > 0.0 and dp_clip == 0.0:
+        raise ValueError("dp_noise > 0 needs a clip norm (dp_clip > 0): the noise is scaled by it")
+    if dp_clip == 0.0:
+        return
+    if prox_mu > 0.0:
+        raise ValueError("FedProx (prox_mu > 0) is not combined with DP-SGD (dp_clip > 0): the DP reduce has no "
+                         "proximal form")
+    if amp_dtype == torch.float16:
+        raise ValueError("DP-SGD does not support fp16 AMP (a GradScaler would rescale the clipped gradients)")
+    if isinstance(model, torch.nn.parallel.DistributedDataParallel):
+        raise ValueError("DP-SGD does not support a DistributedDataParallel model (--sync ddp)")
+    if dp_seed is None:
+        raise ValueError("DP-SGD (dp_clip > 0) in a cohort of virtual clients needs dp_seed, the 64-bit key of its "
+                         "noise: it is not derived from the trainer's seed, which orders the batches, may be None and "
+                         "already keys the client-level close")
 
 
 def client_dp_seed_of(seed: Optional[int], client_dp_seed: Optional[int]) -> int:

@@ -40,7 +40,15 @@ MI355X execution (vs the reference's host-staged per-tensor MPI calls and per-st
     whole cohort in one step launch and one reduce launch per step (``ops.fused_cohort``); ``train.cohort`` is the
     eager reference.  ``samples_per_s`` counts all M * B * S windows of a round; ``batch_size`` in the round rows stays
     the per-client B; rank 0 appends the cohort's shape per round to ``--cohort-csv``.  TinyECG only; not combined
-    with DP-SGD, ``--sync ddp``, ``--drop-prob`` (client sampling replaces it) or ``--overlap delayed``.
+    with ``--sync ddp``, ``--drop-prob`` (client sampling replaces it) or ``--overlap delayed``.
+    With ``--dp-clip`` every virtual client's local steps are DP-SGD steps (record-level DP inside the cohort, whichever
+    close the round has; it needs ``--dp-noise`` > 0, and is not combined with ``--prox-mu``, fp16 AMP or ``--sync ddp``): cohort slot c draws its noise from Philox
+    stream 2 + c of the rank's key (the 64-bit mix of ``seed + 7919 * rank``) and the cohort step counter.  A record of
+    virtual client k is touched only in the rounds that draw k, at sample rate ``B / n_k``: the driver counts the local
+    steps each of the K clients has run (recounted from the sampler on ``--resume``) and reports per round the largest
+    ``epsilon(sigma, B / n_k, steps_k, delta)`` over the rank's clients in the columns of ``--privacy-csv`` (steps and
+    sample rate of that client).  This ignores the amplification by client sampling, which is conservative, and is the
+    same Poisson approximation as for DP-SGD above.
   * ``--client-dp-clip C`` / ``--client-dp-noise sigma`` / ``--client-dp-delta delta`` / ``--server-lr eta``: client-level
     DP on a cohort round (DP-FedAvg; needs ``--clients-per-gpu``).  Every rank clips each of its M clients' round
     deltas to l2 norm C, averages them, adds N(0, (sigma C / (M sqrt(W)))^2) per parameter and applies the result to the
@@ -369,9 +377,10 @@ def check_cohort_config(cfg: FedAvgConfig, backend: str) -> None:
         return
     if backend == "hip" or cfg.model != "tiny_ecg":
         raise ValueError("client sampling (--clients-per-gpu) is implemented for TinyECG, not for ResNet1D models")
-    if cfg.dp_clip > 0:
-        raise ValueError("client sampling (--clients-per-gpu) does not support DP-SGD (--dp-clip): the cohort reduce "
-                         "has no per-sample clip")
+    if cfg.dp_clip > 0 and cfg.dp_noise == 0:
+        raise ValueError("client sampling (--clients-per-gpu) takes DP-SGD (--dp-clip) only together with --dp-noise > 0: "
+                         "clipping alone gives a record no guarantee, and the per-client epsilon this driver reports "
+                         "for a cohort is undefined without noise")
     if cfg.sync == "ddp":
         raise ValueError("client sampling (--clients-per-gpu) does not support --sync ddp: virtual clients are "
                          "averaged per round, not per step")
@@ -452,7 +461,9 @@ def make_trainer(cfg: FedAvgConfig, config_name: str, model, x, y, ctx: DistCont
                   client_dp_clip=cfg.client_dp_clip, client_dp_noise=cfg.client_dp_noise, client_dp_seed=mix64(seed),
                   server_lr=cfg.server_lr, world_size=client_dp_world(cfg, ctx), server_opt=cfg.server_opt,
                   server_beta1=cfg.server_beta1, server_beta2=cfg.server_beta2, server_tau=cfg.server_tau,
-                  server_scope=cfg.server_scope)
+                  server_scope=cfg.server_scope,
+                  dp_clip=cfg.dp_clip, dp_noise=cfg.dp_noise, dp_seed=mix64(seed))  # (stream words 2 + c: apart from
+        # the client-level close's stream 1 under the same key)
         if backend == "fused":
             from ..ops.fused_cohort import FusedCohortTrainer
             prec = "bf16" if (config_name == "G1" and cfg.amp_dtype == "bf16") else "fp32"
@@ -632,6 +643,15 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
         hetero = hetero_on(split_aggregate(cfg)[0]) and cfg.clients_per_gpu > 1
         client_privacy = []  # client-level DP, rank 0: (round, median client norm, clipped share)
         sample_rate = cfg.batch_size / x.shape[0]
+        # record-level DP-SGD in cohort rounds: the local steps each of this rank's K virtual clients has run so far.
+        # The sampler is a pure function of (seed, round), so a resumed run recounts the rounds before it.
+        cohort_dp = cfg.dp_clip > 0 and cfg.clients_per_gpu > 1
+        client_steps = [0] * cfg.clients_per_gpu
+        if cohort_dp:
+            for r0 in range(start_round):
+                ids0 = trainer.sampler.clients_of(r0)
+                for k, sk in zip(ids0, trainer.sampler.steps_of(ids0, cfg.local_epochs)):
+                    client_steps[k] += min(cfg.local_steps, sk)
         for r in range(start_round, cfg.rounds):
             t_round0 = time.perf_counter()
             rec = CommRecord()
@@ -669,8 +689,17 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                 cohorts.append((r, list(trainer.round_clients)))
                 if hetero:
                     shapes.append((r,) + tuple(list(v) for v in trainer.last_round_shape()))
-            if cfg.dp_clip > 0:
-                privacy.append((r, trainer.dp_steps,
+            if cohort_dp:
+                # a record of virtual client k is touched only in the rounds that draw k, at sample rate B / n_k: the
+                # round's figure is the largest epsilon over this rank's clients (no amplification by client sampling)
+                for k, sk in zip(trainer.round_clients, trainer.last_round_shape()[1]):
+                    client_steps[k] += sk
+                privacy.append(max(
+                    ((r, sk, cfg.batch_size / nk, dp_epsilon(cfg.dp_noise, cfg.batch_size / nk, sk, cfg.dp_delta))
+                     for sk, nk in zip(client_steps, map(int, trainer.sampler.sizes_of(range(cfg.clients_per_gpu)))) if sk > 0),
+                    key=lambda t: t[3]))
+            elif cfg.dp_clip > 0:
+                privacy.append((r, trainer.dp_steps, sample_rate,
                                 dp_epsilon(cfg.dp_noise, sample_rate, trainer.dp_steps, cfg.dp_delta)))
             # the stall on the previous round's collective happened inside [m_l0, m_l1]: not local work
             inner = prev_rec.stalls[stalls0:] if prev_rec is not None else []
@@ -738,8 +767,8 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                              f"accuracy {e['accuracy']:.4f} confusion {e['confusion']} ({e['eval_ms']:.2f} ms)")
         if privacy:
             prows = [{"config": cname, "world_size": ctx.world_size, "rank": ctx.rank, "round_idx": r, "steps": steps,
-                      "sample_rate": sample_rate, "noise_multiplier": cfg.dp_noise, "clip_norm": cfg.dp_clip,
-                      "delta": cfg.dp_delta, "epsilon": eps} for r, steps, eps in privacy]
+                      "sample_rate": q, "noise_multiplier": cfg.dp_noise, "clip_norm": cfg.dp_clip,
+                      "delta": cfg.dp_delta, "epsilon": eps} for r, steps, q, eps in privacy]
             for row in prows:
                 log.event("privacy", **row)
             all_prows = comm.gather(prows, root=0)
@@ -752,7 +781,9 @@ def run_fedavg(cfg: FedAvgConfig, ctx: DistContext) -> List[Dict]:
                 log.info(f"[privacy] {cname}: after round {last['round_idx']} ({last['steps']} steps, q="
                          f"{last['sample_rate']:.4g}, sigma={cfg.dp_noise:g}, C={cfg.dp_clip:g}) epsilon <= "
                          f"{last['epsilon']:.4g} at delta={cfg.dp_delta:g} (Poisson-sampling bound; the training "
-                         "loss is not private)")
+                         "loss is not private)" + (
+                             "; record-level, the most exposed virtual client's own steps at q = B / n_k: "
+                             "amplification by client sampling is ignored, which is conservative" if cohort_dp else ""))
         if cohorts and ctx.rank == 0:
             crows = [{"config": cname, "world_size": ctx.world_size, "round_idx": r,
                       "clients_per_gpu": cfg.clients_per_gpu, "cohort": M, "batch_size": cfg.batch_size,

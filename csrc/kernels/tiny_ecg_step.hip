@@ -1296,8 +1296,10 @@ static_assert(kPackLead == 4, "gather_block's 4-float form writes the lead as on
 // the same z: philox4x32_10 with counter (i, t lo, t hi, 0) and key (seed lo, seed hi), i the parameter index and t the
 // 64-bit DP step counter; u1 = ((w0 >> 8) + 1) * 2^-24 in (0, 1], u2 = (w1 >> 8) * 2^-24 in [0, 1),
 // z = sqrt(-2 ln u1) * cos(2 pi u2) with the accurate logf / sqrtf / cosf (|z| <= 5.77).
-__device__ inline float dp_normal(int i, unsigned long long seed, unsigned long long t) {
-  uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)(t >> 32), 0u};
+// ``stream`` is the counter's last word: 0 single-client DP-SGD, 1 client-level DP (tiny_ecg_close.hip), 2 + c the
+// record-level DP-SGD of cohort slot c (c < 65535), so the M clients of one cohort step draw independent vectors.
+__device__ inline float dp_normal(int i, unsigned long long seed, unsigned long long t, uint32_t stream = 0u) {
+  uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)(t >> 32), stream};
   philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
   const float u1 = (float)((c[0] >> 8) + 1u) * 0x1p-24f, u2 = (float)(c[1] >> 8) * 0x1p-24f;
   return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
@@ -1320,6 +1322,9 @@ __device__ inline float dp_normal(int i, unsigned long long seed, unsigned long 
 // graph) - before any parameter, momentum, anchor or slab load and before the barrier; the condition is block-uniform.
 // A client that has finished its local steps is thereby frozen: its weights, momentum, image and loss word are not
 // written, while the step kernel still fills its slab rows and the gather blocks, which leave above, still run.
+// DP && COHORT (record-level DP-SGD inside a cohort): ``scale`` holds M * G clip factors, client c's at scale + c * G
+// (dp_row_scale_cohort_kernel), and client c draws its noise from Philox stream 2 + c of the one step word - after
+// the STEPS return, so a frozen client draws nothing.
 template <int RED_COLS, bool DP, bool COHORT, bool PROX = false, bool STEPS = false>
 __device__ __forceinline__ void slab_reduce_body(
     const float* slab, float* params, float* mom, int nred, int G, int stride, int P, int flags, float momentum,
@@ -1341,6 +1346,7 @@ __device__ __forceinline__ void slab_reduce_body(
       if (step >= client_steps[client]) return;  // block-uniform, before the barrier: a frozen client
     const int pstride = cohort_pstride(P);
     slab += (long)client * G * stride;
+    if constexpr (DP) scale += (long)client * G;
     params += (long)client * pstride;
     mom += (long)client * pstride;  // (only dereferenced when momentum != 0, which needs a momentum buffer)
     if (wprep) wprep += (long)client * kCohortWprepStride;
@@ -1356,8 +1362,12 @@ __device__ __forceinline__ void slab_reduce_body(
   float a0 = 0.f;
   if constexpr (PROX) a0 = upd ? anchor[col] : 0.f;
   float noise = 0.f;  // drawn before the slab reads, under their latency
-  if constexpr (DP)
+  if constexpr (DP && COHORT) {
+    if (rg == 0 && col < P && noise_scale != 0.f)
+      noise = noise_scale * dp_normal(col, seed, dp_step[0] - 1ull, 2u + (uint32_t)client);
+  } else if constexpr (DP) {
     if (rg == 0 && col < P && noise_scale != 0.f) noise = noise_scale * dp_normal(col, seed, dp_step[0] - 1ull);
+  }
   float s = 0.f;
   if (col <= P) {
     const float* base = slab + col;
@@ -1470,6 +1480,41 @@ __global__ __launch_bounds__(ROWS * 64) void dp_row_scale_kernel(
   }
 }
 
+// The clip factors of one cohort step, all M clients in one launch: ``rows`` = M * B slab rows, scale[c * B + b] =
+// min(1, clip / (B * |row|_2)) - the un-scaling is the client's batch size, not the row count.  One advance of the
+// step word per launch, i.e. per cohort step, whichever clients are frozen.  dp_row_scale_kernel's lines with ``rows``
+// as the bound and ``B`` as the factor; a kernel of its own because a shared body changed that kernel's code (two
+// commuted adds), and its machine code is kept as it was.
+template <int ROWS>
+__global__ __launch_bounds__(ROWS * 64) void dp_row_scale_cohort_kernel(
+    const float* __restrict__ slab, int rows, int B, int stride, int P, float clip, float* __restrict__ scale,
+    unsigned long long* __restrict__ dp_step, int vec) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) dp_step[0] = dp_step[0] + 1ull;
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * ROWS + (threadIdx.x >> 6);
+  if (b >= rows) return;  // wave-uniform
+  const float* row = slab + (long)b * stride;
+  float ss = 0.f;
+  if (vec) {
+    for (int c0 = 4 * lane; c0 < P; c0 += 256) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(row + c0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ss += (c0 + j < P) ? v[j] * v[j] : 0.f;
+    }
+  } else {
+    for (int c0 = lane; c0 < P; c0 += 64) {
+      const float v = row[c0];
+      ss += v * v;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  if (lane == 0) {
+    const float n = (float)B * sqrtf(ss);
+    scale[b] = n > 0.f ? fminf(1.f, clip / n) : 1.f;
+  }
+}
+
 // slab_reduce_body's DP form: ``scale`` [G] from dp_row_scale_kernel, noise_scale = sigma * C / B.  The plain
 // kernel's argument order with the DP arguments in front of ``ga``.
 template <int RED_COLS>
@@ -1549,6 +1594,41 @@ __global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_steps_
   slab_reduce_body<RED_COLS, false, true, true, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd,
                                                       wprep, loss_acc, nullptr, nullptr, 0.f, 0ull, nullptr, ga, anchor,
                                                       mu, client_steps, step);
+}
+
+// ---------------------------------------------------------------------------- record-level DP-SGD in a cohort
+// slab_reduce_body's DP && COHORT forms: the cohort kernels' argument lists with ``scale`` [M * G], ``noise_scale`` =
+// sigma * C / G, ``seed`` and ``dp_step`` in front of ``ga`` (and of ``client_steps``, ``step``).  With every factor 1
+// and no noise they leave the bits of the cohort kernels above; a cohort of one without noise those of
+// slab_reduce_dp_sgd_kernel.
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_dp_sgd_kernel(
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
+    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, const float* __restrict__ scale,
+    float noise_scale, unsigned long long seed, const unsigned long long* __restrict__ dp_step, GatherArgs ga) {
+  slab_reduce_body<RED_COLS, true, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd, wprep,
+                                         loss_acc, nullptr, scale, noise_scale, seed, dp_step, ga);
+}
+
+template <int RED_COLS>
+__global__ __launch_bounds__(RED_COLS * RED_ROWG) void slab_reduce_cohort_dp_steps_sgd_kernel(
+    const float* __restrict__ slab, float* __restrict__ params, float* __restrict__ mom, int nred, int G, int stride,
+    int P, int flags, float momentum, float lr, float wd,  // -- preloaded up to here
+    unsigned char* __restrict__ wprep, float* __restrict__ loss_acc, const float* __restrict__ scale,
+    float noise_scale, unsigned long long seed, const unsigned long long* __restrict__ dp_step,
+    const int* __restrict__ client_steps, int step, GatherArgs ga) {
+  slab_reduce_body<RED_COLS, true, true, false, true>(slab, params, mom, nred, G, stride, P, flags, momentum, lr, wd,
+                                                      wprep, loss_acc, nullptr, scale, noise_scale, seed, dp_step, ga,
+                                                      nullptr, 0.f, client_steps, step);
+}
+
+// Diagnostic: dp_noise_kernel with the stream word (2 + c: what client slot c of a cohort DP reduce draws).
+template <int NT>
+__global__ __launch_bounds__(NT) void dp_noise_stream_kernel(float* __restrict__ z, int P, unsigned long long seed,
+                                                             unsigned long long t, uint32_t stream) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i < P) z[i] = dp_normal(i, seed, t, stream);
 }
 
 // anchor[0:P] = params[0:P]: the first launch of a single client's FedProx round.
@@ -1874,6 +1954,38 @@ int cohort_reduce_dispatch(const float* slab, int G, int M, int stride, int P, f
   return ecg::kOk;
 }
 
+// The DP twin of cohort_reduce_dispatch (record-level DP-SGD inside a cohort, no FedProx form): one clip-factor launch
+// over all M * G rows - un-scaling G, one advance of the step word - then the DP cohort reduce, with ``client_steps``
+// its STEPS form.  ``dp.scale`` holds M * G floats.
+int cohort_dp_reduce_dispatch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
+                              float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
+                              const DpArgs& dp, hipStream_t stream, const GatherArgs* gather = nullptr,
+                              const int* client_steps = nullptr, int step = 0) {
+  int st = slab ? check_reduce(G, stride, P, 1, params, momentum, mom) : ecg::kBadArg;
+  if (!st) st = check_dp(dp);
+  if (!st && client_steps && step < 0) st = ecg::kBadArg;
+  if (!st && (long)M * G > INT_MAX) st = ecg::kTooLarge;  // (a round's rows are bounded by check_cohort_round)
+  if (st) return st;
+  const int rows = M * G;
+  const int vec = (stride % 4 == 0 && reinterpret_cast<uintptr_t>(slab) % 16 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(dp_row_scale_cohort_kernel<DP_ROWS_PER_BLOCK>,
+                     dim3((rows + DP_ROWS_PER_BLOCK - 1) / DP_ROWS_PER_BLOCK), dim3(DP_ROWS_PER_BLOCK * 64), 0, stream,
+                     slab, rows, G, stride, P, dp.clip, dp.scale, dp.step, vec);
+  ECG_HIP_CHECK(hipGetLastError());
+  const RedGeom g = red_geom(P, M, gather, true);
+  const float noise_scale = dp.sigma * dp.clip / (float)G;
+  if (client_steps)
+    hipLaunchKernelGGL(slab_reduce_cohort_dp_steps_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0,
+                       stream, slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep,
+                       loss_acc, dp.scale, noise_scale, dp.seed, dp.step, client_steps, step, g.ga);
+  else
+    hipLaunchKernelGGL(slab_reduce_cohort_dp_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream,
+                       slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
+                       dp.scale, noise_scale, dp.seed, dp.step, g.ga);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
+}
+
 struct RoundGraph {
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
@@ -2008,6 +2120,35 @@ ECG_API int ecg_slab_reduce_cohort_steps_sgd(const float* slab, int G, int M, in
   return cohort_reduce_dispatch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov,
                                 static_cast<unsigned char*>(wprep), stream, nullptr, anchor, mu, false, client_steps,
                                 step);
+}
+
+// The record-level DP-SGD twin of ecg_slab_reduce_cohort_steps_sgd (two launches, no FedProx): the clip factors of all
+// M * G rows into ``dp_scale`` [M * G] (un-scaling G) and ``dp_step[0]`` += 1, then per client c the sum of its
+// clipped rows plus dp_sigma * dp_clip / G * z(dp_seed, step, column, stream 2 + c), ``step`` the value ``dp_step[0]``
+// held before the call.  ``client_steps`` is nullable here: null runs every client.  The argument list is
+// ecg_slab_reduce_cohort_steps_sgd's with the DP fields behind ``step``; there is no PROX x DP kernel, so ``mu`` must
+// be 0 and ``anchor`` is not looked at.
+ECG_API int ecg_slab_reduce_cohort_dp_sgd(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
+                                          float* loss_acc, float lr, float momentum, float wd, int nesterov,
+                                          void* wprep, const float* anchor, float mu, const int* client_steps,
+                                          int step, float dp_clip, float dp_sigma, unsigned long long dp_seed,
+                                          float* dp_scale, unsigned long long* dp_step, hipStream_t stream) {
+  (void)anchor;
+  if (!slab || M < 1 || M > 65535 || mu != 0.f) return ecg::kBadArg;
+  return cohort_dp_reduce_dispatch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov,
+                                   static_cast<unsigned char*>(wprep), {dp_clip, dp_sigma, dp_seed, dp_scale, dp_step},
+                                   stream, nullptr, client_steps, step);
+}
+
+// Diagnostic: ecg_dp_noise with the Philox stream word (0: ecg_dp_noise itself; 2 + c: cohort slot c's record-level
+// draw).
+ECG_API int ecg_dp_noise_stream(float* z, int P, unsigned long long seed, unsigned long long t, unsigned stream_word,
+                                hipStream_t stream) {
+  if (!z || P <= 0) return ecg::kBadArg;
+  hipLaunchKernelGGL(dp_noise_stream_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, z, P, seed, t,
+                     (uint32_t)stream_word);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
 }
 
 // A local round: ``steps`` times "step kernel, then reduce + SGD kernel" (DP-SGD: step kernel, clip factors, clipped
@@ -2268,7 +2409,7 @@ ECG_API int ecg_tiny_cohort_wprep_stride(void) { return kCohortWprepStride; }
 // loss_acc[c], slab rows [c * B, (c + 1) * B), columns [c * B, (c + 1) * B) of every ``idx`` row.  bf16 rounds run
 // like a packed EcgTinyRound - the first step builds its operands in LDS, later steps read the images and the packed
 // rows gathered by the previous reduce - and need wprep, xg, yg and xbg, sized for M * B rows
-// (ecg_tiny_gather_floats / _halfs(L, M * B)); fp32 rounds take none of them.  There is no DP-SGD in a cohort.
+// (ecg_tiny_gather_floats / _halfs(L, M * B)); fp32 rounds take none of them.  Record-level DP-SGD: the dp_* fields.
 // The close: with the cdp_* fields, server_lr, server_opt and server_delta all zero (server_lr 1 counts as zero) it is
 // cohort_mean_kernel; anything else - client_weight and robust_trim among it - is ecg::tiny::cohort_close (include/tiny_ecg_close.h), which picks its kernel by
 // server_delta, then server_opt.
@@ -2335,6 +2476,16 @@ struct EcgTinyCohortRound {
   // launches of before.
   int robust_trim;
   float* robust_scratch;
+  // Record-level DP-SGD inside the cohort (dp_clip > 0; not with FedProx): every client's every local step clips its B
+  // per-sample gradients to l2 norm C and adds noise of standard deviation dp_sigma * dp_clip / B per parameter, drawn
+  // from Philox stream 2 + c of (dp_seed, the step word) for cohort slot c - three launches per step (step, clip
+  // factors, DP cohort reduce; cohort_dp_reduce_dispatch).  dp_scale: [M * B] clip factors (scratch); dp_step: the
+  // 64-bit step word (device), advanced once per cohort step whichever clients are frozen.  Independent of the close.
+  // All zero / null: the launches of before.
+  float dp_clip, dp_sigma;
+  unsigned long long dp_seed;
+  float* dp_scale;
+  unsigned long long* dp_step;
 };
 
 ECG_API int ecg_tiny_cohort_round_sizeof(void) { return (int)sizeof(EcgTinyCohortRound); }
@@ -2371,6 +2522,8 @@ static int check_cohort_round(const EcgTinyCohortRound* r) {
   const long rows = (long)r->M * r->B;
   if (rows * r->slab_stride * 4 > INT_MAX || rows * (pack_ldb(r->L) + 8) * 4 > INT_MAX) return ecg::kTooLarge;
   if (r->prox_mu < 0.f) return ecg::kBadArg;
+  if (r->dp_clip < 0.f || r->dp_sigma < 0.f || (r->dp_sigma > 0.f && r->dp_clip == 0.f)) return ecg::kBadArg;
+  if (r->dp_clip > 0.f && (!r->dp_scale || !r->dp_step || r->prox_mu > 0.f)) return ecg::kBadArg;
   if (cohort_close_on(*r)) return check_cohort_close(cohort_close_args(*r));
   // the plain mean reads none of the close's fields; a negative clip norm, or noise without a clip norm, is an error
   return (r->cdp_clip < 0.f || r->cdp_sigma != 0.f) ? ecg::kBadArg : ecg::kOk;
@@ -2398,9 +2551,14 @@ static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream)
     }
     int st = cohort_step_dispatch(r.prec, a, r.M, stream);
     if (st) return st;
-    st = cohort_reduce_dispatch(r.slab, r.B, r.M, r.slab_stride, P, r.params, r.mom, r.loss_acc, r.lr, r.momentum, r.wd,
-                                r.nesterov, wprep, stream, gather_next ? &ga : nullptr, r.global_params, r.prox_mu, false,
-                                r.client_steps, s);
+    if (r.dp_clip > 0.f)
+      st = cohort_dp_reduce_dispatch(r.slab, r.B, r.M, r.slab_stride, P, r.params, r.mom, r.loss_acc, r.lr, r.momentum,
+                                     r.wd, r.nesterov, wprep, {r.dp_clip, r.dp_sigma, r.dp_seed, r.dp_scale, r.dp_step},
+                                     stream, gather_next ? &ga : nullptr, r.client_steps, s);
+    else
+      st = cohort_reduce_dispatch(r.slab, r.B, r.M, r.slab_stride, P, r.params, r.mom, r.loss_acc, r.lr, r.momentum,
+                                  r.wd, r.nesterov, wprep, stream, gather_next ? &ga : nullptr, r.global_params,
+                                  r.prox_mu, false, r.client_steps, s);
     if (st) return st;
   }
   if (cohort_close_on(r)) return cohort_close(cohort_close_args(r), stream);
