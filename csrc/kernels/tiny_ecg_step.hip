@@ -1815,56 +1815,126 @@ int step_dispatch(int mode, int prec, const StepArgs& a, hipStream_t stream) {
   return dispatch_cfg<false, false>(mode, waves, a, stream);
 }
 
-// The argument checks every reduce launch shares.
-int check_reduce(int G, int stride, int P, int apply, const float* params, float momentum, const float* mom) {
-  if (G <= 0 || P <= 0 || stride < P + 1) return ecg::kBadArg;
-  if (apply && (!params || (momentum != 0.f && !mom))) return ecg::kBadArg;
+// ---------------------------------------------------------------------------- the reduce of one step, host side
+// DP-SGD settings of a reduce: clip > 0 (sigma >= 0), the clip-factor vector (one float per slab row) and the device
+// step counter.
+struct DpArgs {
+  float clip, sigma;
+  unsigned long long seed;
+  float* scale;
+  unsigned long long* step;
+};
+
+// One step's reduce + SGD, as check_reduce and launch_reduce take it.  Every reduce has the fields down to ``nesterov``
+// (callers list them); the ones below it are zero unless a caller names them.
+struct Reduce {
+  // the slab: M clients' G rows each (back to back) of ``stride`` floats, P gradient columns and the loss column
+  const float* slab;
+  int G, M, stride, P;
+  // state: client c's weights / momentum at the cohort parameter stride, its image at the cohort image stride and its
+  // loss word loss_acc[c] (a single client: the plain buffers).  mom may be null when momentum == 0; loss_acc and wprep
+  // are nullable
+  float* params;
+  float* mom;
+  float* loss_acc;
+  unsigned char* wprep;
+  // update
+  float lr, momentum, wd;
+  int nesterov;
+  // a single client's reduce only: apply == 0 just sums - into grad_out [P] (nullable, a copy of the summed gradient)
+  // and loss_acc - and then there is no image to keep current
+  int apply;
+  float* grad_out;
+  // the cohort kernel - a cohort of one is still the cohort kernel: the update is always applied (apply is not read),
+  // and there is no grad_out
+  bool cohort;
+  // (nullable) the next step's batch, gathered by this launch's blocks past the reduce blocks
+  const GatherArgs* gather;
+  // FedProx: mu != 0, or ``prox`` (the stand-alone prox entry points: the prox kernel at mu == 0 too), puts
+  // mu * (p - anchor[col]) into the gradient, one anchor [P] for all clients; otherwise the anchor is not looked at
+  const float* anchor;
+  float mu;
+  bool prox;
+  // (nullable; cohort only) [M] int32 on the device: the STEPS kernel, which leaves client c as it is when
+  // step >= client_steps[c]
+  const int* client_steps;
+  int step;
+  // (nullable) DP-SGD: a clip-factor launch in front, then the DP form of the kernel; there is no PROX x DP kernel
+  const DpArgs* dp;
+};
+
+// kOk, or the status of a reduce that launch_reduce must not be given - the forms without a kernel among them.
+int check_reduce(const Reduce& r) {
+  const bool prox = r.prox || r.mu != 0.f;
+  if (r.G <= 0 || r.P <= 0 || r.stride < r.P + 1) return ecg::kBadArg;
+  if (r.cohort ? (r.M < 1 || r.M > 65535 || r.grad_out) : (r.M != 1 || r.client_steps)) return ecg::kBadArg;
+  if ((r.cohort || r.apply) && (!r.params || (r.momentum != 0.f && !r.mom))) return ecg::kBadArg;
+  if (r.wprep && !r.cohort && !r.apply) return ecg::kBadArg;
+  if ((r.cohort || r.dp) && !r.slab) return ecg::kBadArg;  // (the plain entry points never looked at theirs)
+  if (prox && (!r.anchor || r.mu < 0.f || r.dp)) return ecg::kBadArg;
+  if (r.client_steps && r.step < 0) return ecg::kBadArg;
+  if (r.dp && (r.dp->clip <= 0.f || r.dp->sigma < 0.f || !r.dp->scale || !r.dp->step)) return ecg::kBadArg;
+  if (r.dp && (long)r.M * r.G > INT_MAX) return ecg::kTooLarge;  // (a round's rows are bounded by check_cohort_round)
   return ecg::kOk;
 }
 
-// Launch geometry of a reduce over M clients' slabs: ``blocks`` reduce blocks per client (columns 0 .. P,
-// kRedColsDefault per block; A/B: profiles/r1_final/ab_red_cols.txt), then the gather blocks of ``gather`` (nullable,
-// copied into ``ga``).  ``nred`` is the first gather block: M * blocks, or INT_MAX when a single client's reduce has
-// none.
-constexpr int kRedThreads = kRedColsDefault * RED_ROWG;
-struct RedGeom {
-  int blocks, nred, grid;
-  GatherArgs ga;
-};
-RedGeom red_geom(int P, int M, const GatherArgs* gather, bool cohort = false) {
-  RedGeom g{(P + kRedColsDefault) / kRedColsDefault, 0, 0, {}};
-  g.grid = M * g.blocks;
-  g.nred = (gather || cohort) ? g.grid : INT_MAX;
-  if (gather) {
-    g.ga = *gather;
-    const int rpb = gather_rows_per_block(gather_per_row(g.ga), kRedThreads);
-    g.grid += (g.ga.B + rpb - 1) / rpb;
-  }
-  return g;
+// The clip factors of all M * G rows (and the advance of the step word) in front of a DP reduce: the two kernels'
+// launches differ in ``rows`` and the un-scaling divisor, one client's G, only.
+int launch_dp_row_scale(const Reduce& r, hipStream_t stream) {
+  const int rows = r.M * r.G;
+  const int vec = (r.stride % 4 == 0 && reinterpret_cast<uintptr_t>(r.slab) % 16 == 0) ? 1 : 0;
+  const dim3 grid((rows + DP_ROWS_PER_BLOCK - 1) / DP_ROWS_PER_BLOCK), block(DP_ROWS_PER_BLOCK * 64);
+  if (r.cohort)
+    hipLaunchKernelGGL(dp_row_scale_cohort_kernel<DP_ROWS_PER_BLOCK>, grid, block, 0, stream, r.slab, rows, r.G,
+                       r.stride, r.P, r.dp->clip, r.dp->scale, r.dp->step, vec);
+  else
+    hipLaunchKernelGGL(dp_row_scale_kernel<DP_ROWS_PER_BLOCK>, grid, block, 0, stream, r.slab, r.G, r.stride, r.P,
+                       r.dp->clip, r.dp->scale, r.dp->step, vec);
+  ECG_HIP_CHECK(hipGetLastError());
+  return ecg::kOk;
 }
 
-// FedProx (``anchor``, ``mu``; slab_reduce_body's PROX form).
-int check_prox(const float* anchor, float mu) { return (!anchor || mu < 0.f) ? ecg::kBadArg : ecg::kOk; }
-
-// ``mu`` != 0 (or ``prox``, the stand-alone prox entry points): the prox kernel on ``anchor``; otherwise the plain
-// kernel, and ``anchor`` is not looked at.
-int reduce_dispatch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
-                    float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
-                    unsigned char* wprep, hipStream_t stream, const GatherArgs* gather = nullptr,
-                    const float* anchor = nullptr, float mu = 0.f, bool prox = false) {
-  prox = prox || mu != 0.f;
-  int st = check_reduce(G, stride, P, apply, params, momentum, mom);
-  if (!st && prox) st = check_prox(anchor, mu);
+// Check ``r`` and launch it: with DP the clip factors, then exactly one reduce kernel, chosen by (DP, COHORT, PROX,
+// STEPS).  Geometry: (P + 1 columns) / kRedColsDefault reduce blocks per client (A/B: profiles/r1_final/ab_red_cols.txt),
+// then the gather blocks; ``nred`` is the first gather block - M * blocks, or INT_MAX when a single client's reduce
+// has none.
+int launch_reduce(const Reduce& r, hipStream_t stream) {
+  int st = check_reduce(r);
+  if (!st && r.dp) st = launch_dp_row_scale(r, stream);
   if (st) return st;
-  const RedGeom g = red_geom(P, 1, gather);
-  if (prox)
-    hipLaunchKernelGGL(slab_reduce_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
-                       params, mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc,
-                       grad_out, anchor, mu, g.ga);
-  else
-    hipLaunchKernelGGL(slab_reduce_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
-                       params, mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc,
-                       grad_out, g.ga);
+  constexpr int RC = kRedColsDefault, NT = RC * RED_ROWG;
+  int grid = r.M * ((r.P + RC) / RC);
+  const int nred = (r.gather || r.cohort) ? grid : INT_MAX;
+  GatherArgs ga{};
+  if (r.gather) {
+    ga = *r.gather;
+    const int rpb = gather_rows_per_block(gather_per_row(ga), NT);
+    grid += (ga.B + rpb - 1) / rpb;
+  }
+  const int flags = red_flags(r.cohort ? 1 : r.apply, r.nesterov);
+  // every kernel's argument list starts alike (the preloaded dwords and the three pointers behind them); ``tail`` is
+  // what its form adds - grad_out first, where the kernel has one - and ends in ``ga``
+  auto launch = [&](auto kern, auto... tail) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), 0, stream, r.slab, r.params, r.mom, nred, r.G, r.stride, r.P, flags,
+                       r.momentum, r.lr, r.wd, r.wprep, r.loss_acc, tail...);
+  };
+  const bool prox = r.prox || r.mu != 0.f;
+  const int* cs = r.client_steps;
+  if (const DpArgs* d = r.dp) {
+    const float noise_scale = d->sigma * d->clip / (float)r.G;
+    if (!r.cohort) launch(slab_reduce_dp_sgd_kernel<RC>, r.grad_out, d->scale, noise_scale, d->seed, d->step, ga);
+    else if (cs) launch(slab_reduce_cohort_dp_steps_sgd_kernel<RC>, d->scale, noise_scale, d->seed, d->step, cs, r.step, ga);
+    else launch(slab_reduce_cohort_dp_sgd_kernel<RC>, d->scale, noise_scale, d->seed, d->step, ga);
+  } else if (!r.cohort) {
+    if (prox) launch(slab_reduce_prox_sgd_kernel<RC>, r.grad_out, r.anchor, r.mu, ga);
+    else launch(slab_reduce_sgd_kernel<RC>, r.grad_out, ga);
+  } else if (prox) {
+    if (cs) launch(slab_reduce_cohort_steps_prox_sgd_kernel<RC>, r.anchor, r.mu, cs, r.step, ga);
+    else launch(slab_reduce_cohort_prox_sgd_kernel<RC>, r.anchor, r.mu, ga);
+  } else {
+    if (cs) launch(slab_reduce_cohort_steps_sgd_kernel<RC>, cs, r.step, ga);
+    else launch(slab_reduce_cohort_sgd_kernel<RC>, ga);
+  }
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -1872,38 +1942,6 @@ int reduce_dispatch(const float* slab, int G, int stride, int P, float* params, 
 // anchor[0:P] = params[0:P], the first launch of a single client's FedProx round with a snapshot.
 int prox_snapshot_launch(const float* params, float* anchor, int P, hipStream_t stream) {
   hipLaunchKernelGGL(prox_snapshot_kernel<256>, dim3((P + 255) / 256), dim3(256), 0, stream, params, anchor, P);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-// DP-SGD settings of a reduce: clip > 0 (sigma >= 0), the [G] clip-factor vector and the device step counter.
-struct DpArgs {
-  float clip, sigma;
-  unsigned long long seed;
-  float* scale;
-  unsigned long long* step;
-};
-int check_dp(const DpArgs& d) {
-  if (d.clip <= 0.f || d.sigma < 0.f || !d.scale || !d.step) return ecg::kBadArg;
-  return ecg::kOk;
-}
-
-// The DP pair of one step: clip factors (and the counter advance), then the clipped, noised reduce + SGD.
-int dp_reduce_dispatch(const float* slab, int G, int stride, int P, float* params, float* mom, float* grad_out,
-                       float* loss_acc, float lr, float momentum, float wd, int nesterov, int apply,
-                       unsigned char* wprep, const DpArgs& dp, hipStream_t stream, const GatherArgs* gather = nullptr) {
-  int st = slab ? check_reduce(G, stride, P, apply, params, momentum, mom) : ecg::kBadArg;
-  if (!st) st = check_dp(dp);
-  if (st) return st;
-  const int vec = (stride % 4 == 0 && reinterpret_cast<uintptr_t>(slab) % 16 == 0) ? 1 : 0;
-  hipLaunchKernelGGL(dp_row_scale_kernel<DP_ROWS_PER_BLOCK>, dim3((G + DP_ROWS_PER_BLOCK - 1) / DP_ROWS_PER_BLOCK),
-                     dim3(DP_ROWS_PER_BLOCK * 64), 0, stream, slab, G, stride, P, dp.clip, dp.scale, dp.step, vec);
-  ECG_HIP_CHECK(hipGetLastError());
-  const RedGeom g = red_geom(P, 1, gather);
-  const float noise_scale = dp.sigma * dp.clip / (float)G;
-  hipLaunchKernelGGL(slab_reduce_dp_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
-                     params, mom, g.nred, G, stride, P, red_flags(apply, nesterov), momentum, lr, wd, wprep, loss_acc,
-                     grad_out, dp.scale, noise_scale, dp.seed, dp.step, g.ga);
   ECG_HIP_CHECK(hipGetLastError());
   return ecg::kOk;
 }
@@ -1919,71 +1957,6 @@ int cohort_step_dispatch(int prec, const StepArgs& a, int M, hipStream_t stream)
     return w8 ? launch_step<8, 3, false, true, true>(a, stream, M) : launch_step<16, 3, false, true, true>(a, stream, M);
   if (a.wprep) return ecg::kBadArg;  // the unpacked prepared-fragment kernel has no cohort form
   return w8 ? launch_step<8, 3, false, false>(a, stream, M) : launch_step<16, 3, false, false>(a, stream, M);
-}
-
-// The cohort reduce + SGD of one step: M x the plain reduce's blocks, then the gather blocks of the next step.
-// FedProx as in reduce_dispatch, one anchor for all M clients.  ``client_steps`` (nullable, [M] on the device) with
-// ``step``: the STEPS form of either kernel; null: the launches of before.
-int cohort_reduce_dispatch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
-                           float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
-                           hipStream_t stream, const GatherArgs* gather = nullptr, const float* anchor = nullptr,
-                           float mu = 0.f, bool prox = false, const int* client_steps = nullptr, int step = 0) {
-  prox = prox || mu != 0.f;
-  int st = check_reduce(G, stride, P, 1, params, momentum, mom);
-  if (!st && prox) st = check_prox(anchor, mu);
-  if (!st && client_steps && step < 0) st = ecg::kBadArg;
-  if (st) return st;
-  const RedGeom g = red_geom(P, M, gather, true);
-  if (client_steps && prox)
-    hipLaunchKernelGGL(slab_reduce_cohort_steps_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0,
-                       stream, slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep,
-                       loss_acc, anchor, mu, client_steps, step, g.ga);
-  else if (client_steps)
-    hipLaunchKernelGGL(slab_reduce_cohort_steps_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream,
-                       slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
-                       client_steps, step, g.ga);
-  else if (prox)
-    hipLaunchKernelGGL(slab_reduce_cohort_prox_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream,
-                       slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
-                       anchor, mu, g.ga);
-  else
-    hipLaunchKernelGGL(slab_reduce_cohort_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream, slab,
-                       params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
-                       g.ga);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
-}
-
-// The DP twin of cohort_reduce_dispatch (record-level DP-SGD inside a cohort, no FedProx form): one clip-factor launch
-// over all M * G rows - un-scaling G, one advance of the step word - then the DP cohort reduce, with ``client_steps``
-// its STEPS form.  ``dp.scale`` holds M * G floats.
-int cohort_dp_reduce_dispatch(const float* slab, int G, int M, int stride, int P, float* params, float* mom,
-                              float* loss_acc, float lr, float momentum, float wd, int nesterov, unsigned char* wprep,
-                              const DpArgs& dp, hipStream_t stream, const GatherArgs* gather = nullptr,
-                              const int* client_steps = nullptr, int step = 0) {
-  int st = slab ? check_reduce(G, stride, P, 1, params, momentum, mom) : ecg::kBadArg;
-  if (!st) st = check_dp(dp);
-  if (!st && client_steps && step < 0) st = ecg::kBadArg;
-  if (!st && (long)M * G > INT_MAX) st = ecg::kTooLarge;  // (a round's rows are bounded by check_cohort_round)
-  if (st) return st;
-  const int rows = M * G;
-  const int vec = (stride % 4 == 0 && reinterpret_cast<uintptr_t>(slab) % 16 == 0) ? 1 : 0;
-  hipLaunchKernelGGL(dp_row_scale_cohort_kernel<DP_ROWS_PER_BLOCK>,
-                     dim3((rows + DP_ROWS_PER_BLOCK - 1) / DP_ROWS_PER_BLOCK), dim3(DP_ROWS_PER_BLOCK * 64), 0, stream,
-                     slab, rows, G, stride, P, dp.clip, dp.scale, dp.step, vec);
-  ECG_HIP_CHECK(hipGetLastError());
-  const RedGeom g = red_geom(P, M, gather, true);
-  const float noise_scale = dp.sigma * dp.clip / (float)G;
-  if (client_steps)
-    hipLaunchKernelGGL(slab_reduce_cohort_dp_steps_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0,
-                       stream, slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep,
-                       loss_acc, dp.scale, noise_scale, dp.seed, dp.step, client_steps, step, g.ga);
-  else
-    hipLaunchKernelGGL(slab_reduce_cohort_dp_sgd_kernel<kRedColsDefault>, dim3(g.grid), dim3(kRedThreads), 0, stream,
-                       slab, params, mom, g.nred, G, stride, P, red_flags(1, nesterov), momentum, lr, wd, wprep, loss_acc,
-                       dp.scale, noise_scale, dp.seed, dp.step, g.ga);
-  ECG_HIP_CHECK(hipGetLastError());
-  return ecg::kOk;
 }
 
 struct RoundGraph {
@@ -2063,9 +2036,9 @@ ECG_API int ecg_tiny_forward(const float* X, int L, long ldx, const int* idx, co
 ECG_API int ecg_slab_reduce_sgd(const float* slab, int G, int stride, int P, float* params, float* mom,
                                 float* grad_out, float* loss_acc, float lr, float momentum, float wd, int nesterov,
                                 int apply, void* wprep, hipStream_t stream) {
-  if (wprep && !apply) return ecg::kBadArg;
-  return reduce_dispatch(slab, G, stride, P, params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply,
-                         static_cast<unsigned char*>(wprep), stream);
+  Reduce r{slab, G, 1, stride, P, params, mom, loss_acc, static_cast<unsigned char*>(wprep), lr, momentum, wd, nesterov};
+  r.apply = apply, r.grad_out = grad_out;
+  return launch_reduce(r, stream);
 }
 
 // DP-SGD twin of ecg_slab_reduce_sgd (two launches): clip factors of the slab's rows into ``dp_scale`` [G] and
@@ -2075,9 +2048,10 @@ ECG_API int ecg_slab_reduce_dp_sgd(const float* slab, int G, int stride, int P, 
                                    float* grad_out, float* loss_acc, float lr, float momentum, float wd, int nesterov,
                                    int apply, void* wprep, float dp_clip, float dp_sigma, unsigned long long dp_seed,
                                    float* dp_scale, unsigned long long* dp_step, hipStream_t stream) {
-  if (wprep && !apply) return ecg::kBadArg;
-  return dp_reduce_dispatch(slab, G, stride, P, params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply,
-                            static_cast<unsigned char*>(wprep), {dp_clip, dp_sigma, dp_seed, dp_scale, dp_step}, stream);
+  const DpArgs dp{dp_clip, dp_sigma, dp_seed, dp_scale, dp_step};
+  Reduce r{slab, G, 1, stride, P, params, mom, loss_acc, static_cast<unsigned char*>(wprep), lr, momentum, wd, nesterov};
+  r.apply = apply, r.grad_out = grad_out, r.dp = &dp;
+  return launch_reduce(r, stream);
 }
 
 // Diagnostic: z[0:P], the standard normals the DP reduce draws for (seed, step t).
@@ -2093,9 +2067,10 @@ ECG_API int ecg_dp_noise(float* z, int P, unsigned long long seed, unsigned long
 ECG_API int ecg_slab_reduce_prox_sgd(const float* slab, int G, int stride, int P, float* params, float* mom,
                                      float* grad_out, float* loss_acc, float lr, float momentum, float wd, int nesterov,
                                      int apply, void* wprep, const float* anchor, float mu, hipStream_t stream) {
-  if (wprep && !apply) return ecg::kBadArg;
-  return reduce_dispatch(slab, G, stride, P, params, mom, grad_out, loss_acc, lr, momentum, wd, nesterov, apply,
-                         static_cast<unsigned char*>(wprep), stream, nullptr, anchor, mu, true);
+  Reduce r{slab, G, 1, stride, P, params, mom, loss_acc, static_cast<unsigned char*>(wprep), lr, momentum, wd, nesterov};
+  r.apply = apply, r.grad_out = grad_out;
+  r.anchor = anchor, r.mu = mu, r.prox = true;
+  return launch_reduce(r, stream);
 }
 
 // The cohort twin on caller-supplied buffers: M clients' G slab rows each, weights / momenta at the cohort parameter
@@ -2104,9 +2079,10 @@ ECG_API int ecg_slab_reduce_cohort_prox_sgd(const float* slab, int G, int M, int
                                             float* mom, float* loss_acc, float lr, float momentum, float wd,
                                             int nesterov, void* wprep, const float* anchor, float mu,
                                             hipStream_t stream) {
-  if (!slab || M < 1 || M > 65535) return ecg::kBadArg;  // check_cohort_round's range of a cohort
-  return cohort_reduce_dispatch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov,
-                                static_cast<unsigned char*>(wprep), stream, nullptr, anchor, mu, true);
+  Reduce r{slab, G, M, stride, P, params, mom, loss_acc, static_cast<unsigned char*>(wprep), lr, momentum, wd, nesterov};
+  r.cohort = true;
+  r.anchor = anchor, r.mu = mu, r.prox = true;
+  return launch_reduce(r, stream);
 }
 
 // ecg_slab_reduce_cohort_prox_sgd's twin with per-client step counts: the reduce of local step ``step`` (>= 0), which
@@ -2116,10 +2092,12 @@ ECG_API int ecg_slab_reduce_cohort_steps_sgd(const float* slab, int G, int M, in
                                              float* mom, float* loss_acc, float lr, float momentum, float wd,
                                              int nesterov, void* wprep, const float* anchor, float mu,
                                              const int* client_steps, int step, hipStream_t stream) {
-  if (!slab || M < 1 || M > 65535 || !client_steps) return ecg::kBadArg;
-  return cohort_reduce_dispatch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov,
-                                static_cast<unsigned char*>(wprep), stream, nullptr, anchor, mu, false, client_steps,
-                                step);
+  if (!client_steps) return ecg::kBadArg;
+  Reduce r{slab, G, M, stride, P, params, mom, loss_acc, static_cast<unsigned char*>(wprep), lr, momentum, wd, nesterov};
+  r.cohort = true;
+  r.anchor = anchor, r.mu = mu;
+  r.client_steps = client_steps, r.step = step;
+  return launch_reduce(r, stream);
 }
 
 // The record-level DP-SGD twin of ecg_slab_reduce_cohort_steps_sgd (two launches, no FedProx): the clip factors of all
@@ -2134,10 +2112,13 @@ ECG_API int ecg_slab_reduce_cohort_dp_sgd(const float* slab, int G, int M, int s
                                           int step, float dp_clip, float dp_sigma, unsigned long long dp_seed,
                                           float* dp_scale, unsigned long long* dp_step, hipStream_t stream) {
   (void)anchor;
-  if (!slab || M < 1 || M > 65535 || mu != 0.f) return ecg::kBadArg;
-  return cohort_dp_reduce_dispatch(slab, G, M, stride, P, params, mom, loss_acc, lr, momentum, wd, nesterov,
-                                   static_cast<unsigned char*>(wprep), {dp_clip, dp_sigma, dp_seed, dp_scale, dp_step},
-                                   stream, nullptr, client_steps, step);
+  if (mu != 0.f) return ecg::kBadArg;
+  const DpArgs dp{dp_clip, dp_sigma, dp_seed, dp_scale, dp_step};
+  Reduce r{slab, G, M, stride, P, params, mom, loss_acc, static_cast<unsigned char*>(wprep), lr, momentum, wd, nesterov};
+  r.cohort = true;
+  r.client_steps = client_steps, r.step = step;
+  r.dp = &dp;
+  return launch_reduce(r, stream);
 }
 
 // Diagnostic: ecg_dp_noise with the Philox stream word (0: ecg_dp_noise itself; 2 + c: cohort slot c's record-level
@@ -2274,6 +2255,11 @@ static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
   const bool gathers = r.xg || r.prepack == kPrepackGather;
   const GatherBufs bufs{r.xg, r.yg, static_cast<__bf16*>(r.xbg), r.prepack == kPrepackGather ? xpk : nullptr};
   GatherArgs ga = gather_args(r.X, r.ldx, r.Y, r.L, r.B);
+  const DpArgs dp{r.dp_clip, r.dp_sigma, r.dp_seed, r.dp_scale, r.dp_step};
+  Reduce red{r.slab, r.B, 1, r.slab_stride, P, r.params, r.mom, r.loss_acc, wprep, r.lr, r.momentum, r.wd, r.nesterov};
+  red.apply = 1;
+  red.anchor = r.prox_anchor, red.mu = r.prox_mu;  // (check_round: not with DP-SGD)
+  if (r.dp_clip > 0.f) red.dp = &dp;
   for (int s = 0; s < r.steps; ++s) {
     const int* idx = r.idx ? r.idx + (long)s * r.B : nullptr;
     const bool gather_next = gathers && s + 1 < r.steps;
@@ -2287,13 +2273,8 @@ static int enqueue_round(const EcgTinyRound& r, hipStream_t stream) {
     }
     int st = step_dispatch(0, r.prec, a, stream);
     if (st) return st;
-    if (r.dp_clip > 0.f)
-      st = dp_reduce_dispatch(r.slab, r.B, r.slab_stride, P, r.params, r.mom, nullptr, r.loss_acc, r.lr, r.momentum,
-                              r.wd, r.nesterov, 1, wprep, {r.dp_clip, r.dp_sigma, r.dp_seed, r.dp_scale, r.dp_step},
-                              stream, gather_next ? &ga : nullptr);
-    else
-      st = reduce_dispatch(r.slab, r.B, r.slab_stride, P, r.params, r.mom, nullptr, r.loss_acc, r.lr, r.momentum, r.wd,
-                           r.nesterov, 1, wprep, stream, gather_next ? &ga : nullptr, r.prox_anchor, r.prox_mu);
+    red.gather = gather_next ? &ga : nullptr;
+    st = launch_reduce(red, stream);
     if (st) return st;
   }
   return ecg::kOk;
@@ -2479,7 +2460,7 @@ struct EcgTinyCohortRound {
   // Record-level DP-SGD inside the cohort (dp_clip > 0; not with FedProx): every client's every local step clips its B
   // per-sample gradients to l2 norm C and adds noise of standard deviation dp_sigma * dp_clip / B per parameter, drawn
   // from Philox stream 2 + c of (dp_seed, the step word) for cohort slot c - three launches per step (step, clip
-  // factors, DP cohort reduce; cohort_dp_reduce_dispatch).  dp_scale: [M * B] clip factors (scratch); dp_step: the
+  // factors, DP cohort reduce; launch_reduce).  dp_scale: [M * B] clip factors (scratch); dp_step: the
   // 64-bit step word (device), advanced once per cohort step whichever clients are frozen.  Independent of the close.
   // All zero / null: the launches of before.
   float dp_clip, dp_sigma;
@@ -2540,6 +2521,12 @@ static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream)
     ECG_HIP_CHECK(hipGetLastError());
   }
   GatherArgs ga = gather_args(r.X, r.ldx, r.Y, r.L, rows);
+  const DpArgs dp{r.dp_clip, r.dp_sigma, r.dp_seed, r.dp_scale, r.dp_step};
+  Reduce red{r.slab, r.B, r.M, r.slab_stride, P, r.params, r.mom, r.loss_acc, wprep, r.lr, r.momentum, r.wd, r.nesterov};
+  red.cohort = true;
+  red.anchor = r.global_params, red.mu = r.prox_mu;  // (check_cohort_round: not with DP-SGD)
+  red.client_steps = r.client_steps;
+  if (r.dp_clip > 0.f) red.dp = &dp;
   for (int s = 0; s < r.steps; ++s) {
     const int* idx = r.idx + (long)s * rows;
     const bool gather_next = bf16 && s + 1 < r.steps;
@@ -2551,14 +2538,8 @@ static int enqueue_cohort_round(const EcgTinyCohortRound& r, hipStream_t stream)
     }
     int st = cohort_step_dispatch(r.prec, a, r.M, stream);
     if (st) return st;
-    if (r.dp_clip > 0.f)
-      st = cohort_dp_reduce_dispatch(r.slab, r.B, r.M, r.slab_stride, P, r.params, r.mom, r.loss_acc, r.lr, r.momentum,
-                                     r.wd, r.nesterov, wprep, {r.dp_clip, r.dp_sigma, r.dp_seed, r.dp_scale, r.dp_step},
-                                     stream, gather_next ? &ga : nullptr, r.client_steps, s);
-    else
-      st = cohort_reduce_dispatch(r.slab, r.B, r.M, r.slab_stride, P, r.params, r.mom, r.loss_acc, r.lr, r.momentum,
-                                  r.wd, r.nesterov, wprep, stream, gather_next ? &ga : nullptr, r.global_params,
-                                  r.prox_mu, false, r.client_steps, s);
+    red.gather = gather_next ? &ga : nullptr, red.step = s;
+    st = launch_reduce(red, stream);
     if (st) return st;
   }
   if (cohort_close_on(r)) return cohort_close(cohort_close_args(r), stream);
